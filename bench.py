@@ -1,5 +1,11 @@
 #!/usr/bin/env python
-"""bench.py — headline benchmark of the hot path on MI355X, plus every BASELINE config in the same JSON line.
+"""bench.py — headline benchmark of the hot path on MI355X; with --full, every BASELINE config in the same JSON line.
+
+A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, runs W warm-up steps and EXACTLY K timed steps in one block,
+writes the last timed step's outputs when --dump-outputs DIR is given, and prints the line: the contract's keys and the
+headline's `roofline` from the HIP events of that block.  Everything else described below — `cold_ms`,
+the two extra spread blocks, `parity_checked` / `cpu_baseline` / `cpu_optimised_multicore`, `configs`, the drop-in rows and
+`upload`, the live `roofline.traffic` passes, the N > 1 preflight and `result_check` — runs only with --full.
 
 Headline (BASELINE.json `metric`: "rows/s + achieved HBM GB/s, 10^9-row filter→hash-agg"):
 
@@ -72,16 +78,23 @@ def parse(argv=None):
     ap.add_argument("--reserve-gb", type=float, default=32.0, help="nqe_ctx_reserve: device memory the context takes from the driver at start-up and serves its outputs "
                                                                     "and scratch from (0 = none: every first allocation is a hipMalloc)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-preflight", action="store_true", help="N > 1: skip the communicator self-test that runs before the big allocations")
+    ap.add_argument("--no-preflight", action="store_true", help="N > 1 with --full: skip the communicator self-test that runs before the big allocations")
     ap.add_argument("--preflight-timeout", type=float, default=180.0, help="seconds a preflight stage may take before the rank reports where it is stuck and exits")
     ap.add_argument("--no-configs", action="store_true", help="only the main workload's line (no `configs` block)")
-    ap.add_argument("--no-live-traffic", action="store_true", help="do not measure `roofline.traffic` with rocprofv3 --pmc child passes after the timed region (the default run does; quoted figure only)")
+    ap.add_argument("--no-live-traffic", action="store_true", help="do not measure `roofline.traffic` with rocprofv3 --pmc child passes after the timed region (the --full run does; quoted figure only)")
     ap.add_argument("--only", default="", help="comma-separated side configs to run (default: all)")
     ap.add_argument("--cpu-threads", type=int, default=-1, help="threads of the OPTIONAL second CPU number of the headline — an optimised multi-core form, not the reference's "
                                                                 "single-threaded algorithm (0 = skip, -1 = min(64, host cores))")
     ap.add_argument("--cpu-sample-rows", type=int, default=150_000_000, help="rows of the CPU baseline sample (about 10 s of single-thread work for the headline)")
     ap.add_argument("--details", default="", help="write the full per-config records (per-kernel times, workload text) to this file")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true", help="also the cold first execution, spread blocks, CPU baselines and oracle parity, every side config, "
+                                                        "the drop-in rows and the live counter passes (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the output table(s) of the last timed step of the main workload as DIR/<name>.npy "
+                                                                      "(float64; a fixed seeded row sample above 64 MB in all)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def free_port():
@@ -93,7 +106,10 @@ def free_port():
 
 
 def self_launch(args):
-    """`python bench.py --gpus N` without a launcher: one rank per device under torch.distributed.run; never returns"""
+    """`python bench.py --gpus N` without a launcher: one rank per device under torch.distributed.run, in a child process (this
+    one may have opened the GPU to count devices, so it is not replaced); exits with the launcher's status, never returns"""
+    import subprocess
+
     import torch
 
     have = torch.cuda.device_count()
@@ -103,7 +119,8 @@ def self_launch(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
            "--master-port", str(free_port()), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    rc = subprocess.call(cmd)
+    sys.exit(rc if rc >= 0 else 128 - rc)  # (killed by signal s: the shell's 128 + s)
 
 
 class F:
@@ -243,7 +260,7 @@ class Bench:
         if self.distributed:
             # the data path's own communicator, on the context's stream: RCCL, or the host-staged transport — created and SELF-TESTED
             # (preflight) before anything large is allocated: the first contact of N real RCCL peers should cost seconds to diagnose
-            if args.no_preflight:
+            if args.no_preflight or not args.full:
                 self.comm = parallel.make_staged_comm(self.ctx) if self.host_transport else parallel.make_comm(self.ctx)
             else:
                 self.preflight = preflight(self, parallel)
@@ -260,6 +277,8 @@ class Bench:
                 sys.stderr.write(f"bench.py: nqe_ctx_reserve({args.reserve_gb} GB) failed ({e}); continuing without a reserved block\n")
         self.keep = []
         self.min_warm_s = 0.0
+        # --dump-outputs: _block keeps the output of its last step here (the main workload only: side configs run with it off)
+        self.keep_last, self.last_out = bool(args.dump_outputs), None
 
     def synth(self, kind, seed, rows, first_row=0, mod=1, base=0, dtype=None):
         """a synthetic column in a torch tensor, filled by the library's generator on the CONTEXT's stream.  Set-up code, fully
@@ -315,12 +334,15 @@ class Bench:
     def _block(self, step, steps):
         """exactly K steps between barrier + synchronize on both sides; max over ranks.  Kernel times come from HIP events the
         library records around every launch on its stream while timing is enabled."""
+        self.last_out = None
         self.barrier()
         self.ctx.timing_enable(True)
         self.ctx.timing_reset()
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for i in range(steps):
             r = step()
+            if self.keep_last and i == steps - 1:
+                self.last_out = r
             del r
         self.barrier()
         dt = time.perf_counter() - t0
@@ -333,9 +355,10 @@ class Bench:
         """→ (ms per step, kernels, spread).  blocks = 1: the contract's W warm-up steps + exactly K timed steps.  blocks > 1 (the
         side configs): that many timed blocks of K steps behind one warm-up; the MEDIAN block is reported (its ms and its kernel
         times), with min/max over the blocks as `spread`.  `spread_blocks` more blocks of K steps follow the reported one(s) and
-        feed ONLY the spread (the main line: its value is the contract's single block, its roofline says how far two more moved)."""
+        feed ONLY the spread (the main line under --full: its value is the contract's single block, its roofline says how far two
+        more moved; a plain run times the one block only)."""
         if spread_blocks is None:
-            spread_blocks = 2 if blocks == 1 else 0
+            spread_blocks = 2 if blocks == 1 and self.args.full else 0
         self._warm(step, warmup)
         runs = [self._block(step, steps) for _ in range(blocks)]
         more = [self._block(step, steps) for _ in range(spread_blocks)]
@@ -661,7 +684,10 @@ def wl_aggregate(B, rows, with_filter, random_keys, steps, warmup, groups=None, 
     names = ["agg_grouped", "agg_merge_partials", "agg_fold_partials", "agg_partition", "agg_slab", "agg_segments", "agg_range", "agg_subpartition", "agg_sample", "expr_tree", "keep_from"]
     res = {"metric": "filter_hash_aggregate_rows_per_s" if use_pred else "hash_aggregate_rows_per_s", "value": total / (ms * 1e-3), "unit": "rows/s",
            "ms_per_step": ms, "spread": spread, "cold_ms": cold_ms, "workload": desc, "rows_per_gpu": n, "roofline": roofline(sh["bpr"] * n, kernels, names)}
-    return res, dict(table=table, tens=tens, valid=valid, sh=sh, key=key, fields=fields, n=n, total=total, use_pred=use_pred, random_keys=random_keys, groups=groups)
+    # (--dump-outputs: the output columns are named `<func>_<column>`; the sharded form also returns the group keys)
+    out_names = [[f"{AGG(f).name.lower()}_{sh['cols'][c][0]}" for f, c in sh["aggs"]], ["group_key"]]
+    return res, dict(table=table, tens=tens, valid=valid, sh=sh, key=key, fields=fields, n=n, total=total, use_pred=use_pred, random_keys=random_keys, groups=groups,
+                     out_names=out_names)
 
 
 def parity_aggregate(B, st, sample_rows):
@@ -1353,6 +1379,49 @@ def sharded_headline_check(B, st):
     return {"ok": bool(int(okt.item())), "what": "sharded headline on every rank: 1024 keys, analytic counts, avg = sum / count, min/max in [0, 100)"}
 
 
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_LIMIT = 64 << 20  # bytes of all arrays one --dump-outputs run writes
+
+
+def output_arrays(result, names=None):
+    """the output table(s) one step returned (a table, or the sharded operators' (table, keys)) → {name: float64 array}, as the
+    caller receives them (row order included; NULL → NaN).  `names`: one list of column names per table, else t<i>_c<j>."""
+    import numpy as np
+
+    from naive_query_engine_amd import DType
+
+    tables = [t for t in (result if isinstance(result, tuple) else (result,)) if t is not None]
+    arrays = {}
+    for ti, t in enumerate(tables):
+        for ci, c in enumerate(t.to_host()):
+            if c.dtype == DType.UTF8:
+                raise NotImplementedError("--dump-outputs: Utf8 output columns")
+            a = c.to_numpy().astype(np.float64)
+            if c.validity is not None:
+                a[~c.valid_mask()] = np.nan
+            arrays[names[ti][ci] if names and ti < len(names) else f"t{ti}_c{ci}"] = a
+    return arrays
+
+
+def dump_outputs(arrays, dirname, limit=DUMP_LIMIT):
+    """arrays → DIR/<name>.npy.  Above `limit` bytes in all, every array keeps the same rows: a sample of its row count drawn with a
+    fixed seed (DIR/sample_rows.npy: their indices, ascending), so that runs with the same arguments write the same rows."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    if sum(a.nbytes for a in arrays.values()) > limit:
+        lengths = {len(a) for a in arrays.values()}
+        if len(lengths) != 1:
+            raise ValueError(f"--dump-outputs: cannot sample output columns of different lengths {sorted(lengths)}")
+        n = lengths.pop()
+        k = limit // 8 // (len(arrays) + 1)
+        rows = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+        arrays = dict({name: a[rows] for name, a in arrays.items()}, sample_rows=rows.astype(np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+    return sorted(arrays)
+
+
 # ------------------------------------------------------------------------------------------------ main
 def main():
     args = parse()
@@ -1379,7 +1448,7 @@ def main():
     default_rows = {"headline": 10**9, "headline_int64": 10**9, "headline_single": 10**9, "agg3": 10**9, "agg_readme": 10**9, "headline_nullable": 10**9, "tree_pred": 10**9,
                     "c3": 10**9}.get(wl, 10**8)
     n = args.rows or default_rows
-    want_cpu = world == 1 and not args.no_cpu_baseline
+    want_cpu = args.full and world == 1 and not args.no_cpu_baseline
     par_threads = args.cpu_threads if args.cpu_threads > 0 else max(1, min(64, os.cpu_count() or 1))  # the full-size CPU form of the parity checks
     csteps, cwarm, cblocks = max(3, min(args.steps, 10)), 2, 3  # the side configs: three blocks of a few steps each
 
@@ -1388,7 +1457,7 @@ def main():
                   "tree_pred": ("tree", True), "agg_readme": ("readme", False), "headline_nullable": ("vnull", True)}
     if wl in agg_shapes:
         shape, filt = agg_shapes[wl]
-        res, st = wl_aggregate(B, n, filt, args.random_keys, args.steps, args.warmup, shape=shape, cold=True)
+        res, st = wl_aggregate(B, n, filt, args.random_keys, args.steps, args.warmup, shape=shape, cold=args.full)
         par = parity_aggregate_both(B, st, args.cpu_sample_rows if wl == "headline" else 20_000_000, par_threads) if want_cpu else None
         name = {"headline_int64": "headline_int64_values", "headline_single": "headline_single_column", "agg3": "agg_three_value_columns", "agg_readme": "agg_readme_shape",
                 "tree_pred": "agg_tree_predicate"}.get(wl, wl) + ("_random_keys" if args.random_keys else "")
@@ -1413,6 +1482,10 @@ def main():
             name = "c4_shared_probe_columns"
         if wl == "c4" and args.dim_rows != 10**6:
             name = {10**7: "c4_dim_1e7", 10**8: "c4_dim_1e8"}.get(args.dim_rows, name)
+    if args.dump_outputs:
+        if rank == 0:
+            dump_outputs(output_arrays(B.last_out, st.get("out_names")), args.dump_outputs)
+        B.keep_last, B.last_out = False, None
     attach_traffic(res["roofline"], name)
     attach_spread(res)
     n_main = res["rows_per_gpu"]
@@ -1442,13 +1515,13 @@ def main():
         out["parity_checked"], out["cpu_baseline"] = par
     if par and wl == "headline" and not args.random_keys and args.cpu_threads != 0:
         out["cpu_optimised_multicore"] = cpu_multicore_headline(st, args.cpu_threads if args.cpu_threads > 0 else min(64, os.cpu_count() or 1), args.cpu_sample_rows)
-    if B.comm is not None and wl == "headline" and not args.random_keys and args.pass_frac == 0.5:
+    if args.full and B.comm is not None and wl == "headline" and not args.random_keys and args.pass_frac == 0.5:
         out["result_check"] = sharded_headline_check(B, st)
-    main_state = st if (wl == "headline" and not args.no_configs and not args.random_keys and world == 1) else None
+    main_state = st if (args.full and wl == "headline" and not args.no_configs and not args.random_keys and world == 1) else None
     del st
 
-    # ---- every other config, in the same line
-    if wl == "headline" and not args.no_configs and not args.random_keys:
+    # ---- every other config, in the same line (--full)
+    if args.full and wl == "headline" and not args.no_configs and not args.random_keys:
         cfg = {}
         only = set(x for x in args.only.split(",") if x)
         B.min_warm_s = 0.15
@@ -1562,7 +1635,7 @@ def main():
             up_rec.pop("what", None)
         out["configs"] = cfg
 
-    if rank == 0 and world == 1 and wl == "headline" and not (args.no_configs or args.random_keys or args.no_live_traffic or args.rows) and args.pass_frac == 0.5:
+    if args.full and rank == 0 and world == 1 and wl == "headline" and not (args.no_configs or args.random_keys or args.no_live_traffic or args.rows) and args.pass_frac == 0.5:
         # everything timed is done: the counters are collected by child processes (rocprofv3 cannot attach to this one) — the headline and
         # BASELINE's other single-GPU configs
         lt = LiveTraffic()

@@ -4,6 +4,9 @@ import json
 import os
 import sys
 
+import numpy as np
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
@@ -154,3 +157,53 @@ def test_live_traffic_stops_at_its_time_budget_and_after_a_failed_pass(monkeypat
     lt.close()
     assert len(calls) == 1, calls   # the second config did not try again
     assert r1["traffic"] == 1.0 and r2["traffic"] == 1.0 and "exited with 1" in r2["traffic_live"]
+
+
+def test_plain_run_is_the_default_and_steps_are_checked():
+    a = bench.parse([])
+    assert a.full is False and a.dump_outputs == ""
+    a = bench.parse(["--full", "--dump-outputs", "out", "--steps", "7", "--warmup", "0"])
+    assert a.full and a.dump_outputs == "out" and a.steps == 7 and a.warmup == 0
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse(bad)
+
+
+class FakeTable:
+    def __init__(self, cols):
+        self.cols = cols
+
+    def to_host(self):
+        return self.cols
+
+
+def test_dump_outputs_writes_named_float64_arrays(tmp_path):
+    from naive_query_engine_amd import Column
+
+    cnt = Column.from_numpy(np.array([3, 0, 2**40], dtype=np.uint64))
+    s = Column.from_numpy(np.array([1.5, -2.0, 7.25]), mask=np.array([True, False, True]))
+    keys = Column.from_numpy(np.array([0, 1, 2], dtype=np.int64))
+    arrays = bench.output_arrays((FakeTable([cnt, s]), FakeTable([keys])), [["count_v", "sum_v"], ["group_key"]])
+    assert bench.dump_outputs(arrays, str(tmp_path / "d")) == ["count_v", "group_key", "sum_v"]
+    got = {n: np.load(tmp_path / "d" / f"{n}.npy") for n in ("count_v", "sum_v", "group_key")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["count_v"].tolist() == [3.0, 0.0, float(2**40)] and got["group_key"].tolist() == [0.0, 1.0, 2.0]
+    assert got["sum_v"][0] == 1.5 and np.isnan(got["sum_v"][1]) and got["sum_v"][2] == 7.25
+    # one table without names (the other workloads): t<i>_c<j>
+    assert sorted(bench.output_arrays(FakeTable([keys]))) == ["t0_c0"]
+
+
+def test_dump_outputs_samples_the_same_rows_above_the_limit(tmp_path):
+    n = 100_000
+    arrays = {"a": np.arange(n, dtype=np.float64), "b": -np.arange(n, dtype=np.float64)}
+    limit = 24_000                                  # 1.6 MB of arrays: 1000 rows of each, and their indices
+    for d in ("x", "y"):
+        assert bench.dump_outputs(arrays, str(tmp_path / d), limit=limit) == ["a", "b", "sample_rows"]
+    rows = np.load(tmp_path / "x" / "sample_rows.npy")
+    assert len(rows) == 1000 and (np.diff(rows) > 0).all() and rows[-1] < n
+    assert (np.load(tmp_path / "x" / "a.npy") == rows).all() and (np.load(tmp_path / "x" / "b.npy") == -rows).all()
+    assert sum(os.path.getsize(tmp_path / "x" / f) - 128 for f in os.listdir(tmp_path / "x")) <= limit   # (128 B: the .npy header)
+    for f in ("a.npy", "b.npy", "sample_rows.npy"):
+        assert (tmp_path / "x" / f).read_bytes() == (tmp_path / "y" / f).read_bytes()
+    with pytest.raises(ValueError):
+        bench.dump_outputs({"a": np.zeros(n), "b": np.zeros(n - 1)}, str(tmp_path / "z"), limit=limit)

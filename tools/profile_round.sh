@@ -13,7 +13,7 @@ python tools/csrc_rev.py > $OUT/csrc_rev.txt
 LIGHT=${NQE_PROFILE_LIGHT:-}
 if [ -z "$LIGHT" ]; then
 # the same line with nothing remembered between executions (every execution plans from scratch; the key sample still runs)
-NQE_NO_PLAN_HINTS=1 python bench.py --details $OUT/bench_details_no_plan_hints.json 2>&1 | tail -1 > $OUT/bench_no_plan_hints.json
+NQE_NO_PLAN_HINTS=1 python bench.py --full --details $OUT/bench_details_no_plan_hints.json 2>&1 | tail -1 > $OUT/bench_no_plan_hints.json
 # first-execution cost of every query shape, each in a fresh process
 NQE_COLD_VARIANTS=NQE_NO_RESERVE,NQE_LAZY_MODULES python tools/probe_cold.py 2>&1 | grep -v amdgpu.ids > $OUT/probe_cold.txt
 fi
@@ -40,7 +40,7 @@ cd $R
 # the default line LAST among the measurements it quotes: summarised here, on the box, the PMC passes above are what its `roofline.traffic` is
 # quoted from (bench.py only quotes a file made from the csrc revision that is running)
 python tools/summarize_profiles.py $TAG > /dev/null 2>&1
-python bench.py --details $OUT/bench_details.json 2>&1 | tail -1 > $OUT/bench_default.json
+python bench.py --full --details $OUT/bench_details.json 2>&1 | tail -1 > $OUT/bench_default.json
 if [ -n "$LIGHT" ]; then ls $OUT; exit 0; fi
 python tools/probe_paths.py groups 2>&1 | grep -v amdgpu.ids > $OUT/probe_groups.txt
 python tools/probe_paths.py joinshapes 2>&1 | grep -v amdgpu.ids > $OUT/probe_joinshapes.txt
