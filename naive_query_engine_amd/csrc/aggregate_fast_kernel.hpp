@@ -28,6 +28,12 @@
 #ifndef NQE_AGG_RUN_BUDGET
 #define NQE_AGG_RUN_BUDGET 32 // tile pairs between two looks at the keys while in the run loop
 #endif
+#ifndef NQE_PRED_SKIP
+#define NQE_PRED_SKIP 1 // 0: every tile's value words are loaded whatever the range predicate says (A/B runs)
+#endif
+#ifndef NQE_SKIP_DEPTH
+#define NQE_SKIP_DEPTH 4 // tiles of test words in flight per wave in the key-only loop (8 VGPRs per tile at four rows per lane)
+#endif
 
 namespace nqe {
 namespace agg {
@@ -45,7 +51,10 @@ namespace {
 //   * loads are unconditional (row index clamped to n-1): no exec-mask branches around them;
 //   * PIPE: the NEXT tile's words are requested before the current tile is processed (two register
 //     tiles), so waits are counted `s_waitcnt vmcnt(k)` and a wave keeps a tile in flight while it
-//     computes.
+//     computes;
+//   * SKIP (range test on the key column or on the predicate column, NQE_PRED_SKIP): a tile none of whose rows of the wave
+//     passes sends the wave into a key-only loop that reads just the tested words until a tile with a passing row comes up
+//     (`id < N/2` over row numbers: the upper half's value words are never read).
 // PRED: 0 none, 1 range test on the key column itself (one load serves both), 2 on another column, 3 a fault-free integer chain
 // `col op lit … cmp lit` over any column, interpreted operator-major like the KEY = 3 keys, 4 `A and B` / `A or B` of two range
 // tests over the key column, the first value column and at most one more column (AggArgs::conj), 5 any other fault-free predicate
@@ -72,6 +81,16 @@ __global__ void __launch_bounds__(AGG_BLOCK) agg_grouped_fast_kernel(AggArgs a, 
     constexpr int NVL = FK ? NVT - 1 : NVT; // value columns the tile loads
     // (key subsets: 2 rows per lane 0.59 ms at 6000 groups, 4: 0.49, 8: 0.46-0.47 and 3 MB more code — profiles/r06/ab_sub_plain_loads.txt)
     constexpr int TU = SH1 ? 2 * AGG_U : ((NQE_WIDE_TILES && NVT == 1 && !VNULL && !SUB && PRED <= 1 && KEY != 3) ? NQE_WIDE_TILES : AGG_U); // rows per lane per tile
+    // PIPE: a prefetched second tile (see `stream`).  (PRED = 6: ONE tile in flight — the stack machine's registers take the place of
+    // the prefetched tile's; the workgroup's 16 waves hide the loads' latency among themselves.)  (Three value columns: one tile is
+    // 6-8 KB per wave = 96-128 KB per CU in flight already; a second one spills ~30 VGPRs.)
+    constexpr bool PIPE = (PRED != 6 || NQE_TREE_PIPE) && (NVT != 3 || FK) && (!ML || NQE_ML_PIPE);
+    // SKIP: a range test whose words the tile loads anyway in front of value words of another column — the tested words alone tell
+    // which tiles need their value words (see `skip_tiles`; the code takes PRED = 2, the predicate column's words, as well).  Only the
+    // instances where the key-only loop costs no spill: one Float64 value column under the key-range test (the headline's shape).
+    // Elsewhere the loop beside the row loops' registers spilled 8-91 VGPRs (Int64 values: 14, two value columns: 36, PRED = 2: 67-91
+    // — at NQE_SKIP_DEPTH 2 as many).
+    constexpr bool SKIP = NQE_PRED_SKIP && PRED == 1 && !SH1 && !VNULL && !SUB && PIPE && NVT == 1 && VF64;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const uint32_t cap = uint32_t(a.lds_cap);
     const uint32_t slots = cap + 1;
@@ -457,6 +476,7 @@ __global__ void __launch_bounds__(AGG_BLOCK) agg_grouped_fast_kernel(AggArgs a, 
         uint64_t keys[KEY == 3 ? TU : 1];
         if (KEY == 3) inline_keys<3, TU>(a.key, t.kw, reinterpret_cast<uint64_t (&)[TU]>(keys), key_mask, key_aux, key_signed);
         const uint32_t nrows = tile_rows(base);
+        bool any = false; // a row of the lane passes (SKIP: the wave's ballot of it is the return value)
 #pragma unroll
         for (int u = 0; u < TU; ++u) {
             int64_t row = base + int64_t(u) * AGG_BLOCK + threadIdx.x;
@@ -469,9 +489,11 @@ __global__ void __launch_bounds__(AGG_BLOCK) agg_grouped_fast_kernel(AggArgs a, 
             }
             if (VNULL) pass = pass && ((t.kpv[u] >> (row & 63)) & 1ull);
             const uint64_t key = KEY == 3 ? keys[KEY == 3 ? u : 0] : inline_key<KEY>(a.key, t.kw[u], key_mask, key_aux, key_signed);
+            any = any || pass;
             if (!pass) continue;
             accumulate_row(t, u, row, key);
         }
+        return !SKIP || __ballot(any) != 0;
     };
     auto tile_keys = [&](const Tile &t, uint64_t (&key)[TU]) {
         if (KEY == 3) inline_keys<3, TU>(a.key, t.kw, key, key_mask, key_aux, key_signed);
@@ -517,15 +539,81 @@ __global__ void __launch_bounds__(AGG_BLOCK) agg_grouped_fast_kernel(AggArgs a, 
             for (int u = 0; u < TU; ++u)
                 if (pass[u]) accumulate_row(t, u, base + int64_t(u) * AGG_BLOCK + threadIdx.x, key[u]);
         }
+        return true; // (a wave whose keys differ inside a tile streams on: only the run loop hands over to the key-only loop)
     };
 
     const int64_t stride = int64_t(lanes) * step;
     int64_t base = int64_t(lane_id) * step;
-    // up to 2 x `budget` tiles.  In: A holds tile `base` (< n).  Out: base >= n (done or abandoned), or A holds tile `base`.
-    // (PRED = 6: ONE tile in flight — the stack machine's registers take the place of the prefetched tile's; the workgroup's 16
-    // waves hide the loads' latency among themselves)
-    // (three value columns: one tile is 6-8 KB per wave = 96-128 KB per CU in flight already; a second one spills ~30 VGPRs)
-    constexpr bool PIPE = (PRED != 6 || NQE_TREE_PIPE) && (NVT != 3 || FK) && (!ML || NQE_ML_PIPE);
+    // SKIP: the key-only loop.  The row loops report whether any row of the wave passed the tile's range test (the pass bits they
+    // compute anyway, one ballot); a tile without one sets `miss`, and the wave then streams only the tested words — NQE_SKIP_DEPTH
+    // tiles of them in flight, as many bytes as the two full tiles of the row loops — until a tile with a passing row comes up, whose
+    // words are then loaded whole.  The loads stay unconditional (clamped) and the exits wave-uniform, so every wait in the loop is a
+    // counted one.  What a wrong guess costs: one prefetched tile's value words on the way in, up to NQE_SKIP_DEPTH tiles of test words
+    // on the way out (predicates that flip from tile to tile pay that on every flip).
+    bool miss = false;
+    constexpr int SD = SKIP ? NQE_SKIP_DEPTH : 1;
+    // the tested words of tile `b` (the key words, PRED = 1; the predicate column's words or bitmap words, PRED = 2): scalar tile
+    // pointer + 32-bit lane offset for every tile — a partial tile or one past the end reads its last row (index clamped in 32 bits, no
+    // per-lane 64-bit form: that one, beside the run loop's registers, spilled)
+    auto load_test = [&](uint64_t (&w)[TU], int64_t b) {
+        const uint64_t *__restrict__ src = PRED == 2 ? predp : keyp;
+        const uint32_t nrows = tile_rows(b), lim = nrows ? nrows - 1 : 0;
+        const int64_t tb = b < n ? b : last;
+        const uint64_t *__restrict__ t = src + (PRED == 2 ? (tb >> fp.row_shift) : tb);
+#pragma unroll
+        for (int u = 0; u < TU; ++u) {
+            const uint32_t r = lane_row[u] < lim ? lane_row[u] : lim;
+            const uint32_t i = PRED == 2 ? (r >> fp.row_shift) : r;
+            w[u] = NT ? __builtin_nontemporal_load(&t[i]) : t[i];
+        }
+    };
+    // a row of tile `b` in the wave passes (wave-uniform)
+    auto test_hit = [&](const uint64_t (&w)[TU], int64_t b) {
+        const uint32_t nrows = tile_rows(b);
+        bool any = false; // (`|` and `&`: no exec-mask branch per row)
+#pragma unroll
+        for (int u = 0; u < TU; ++u) {
+            const int64_t row = b + int64_t(u) * AGG_BLOCK + threadIdx.x;
+            any = any | ((lane_row[u] < nrows) & range_pass(fp, PRED == 1 ? w[u] : pred_extract(fp, w[u], row)));
+        }
+        return __ballot(any) != 0;
+    };
+    // In: A holds tile `base` (< n).  Out: base >= n, or A holds tile `base` and a row of it in the wave passes.
+    // The loop body is straight-line — every slot's words are waited for, tested and requested again (the tiles past a hit are then
+    // wasted words, at most NQE_SKIP_DEPTH tiles), and the one exit test sits at the bottom: an exit from the middle of the body
+    // joined the loop's latch, and the waits there became vmcnt(0) (all NQE_SKIP_DEPTH tiles drained once per pass).
+    auto skip_tiles = [&](Tile &A) {
+        if constexpr (SKIP) {
+            if (test_hit(PRED == 1 ? A.kw : A.pw, base)) return;
+            // (nothing in flight, the row loops' flag loads included: a FLAT load still counted as pending makes the compiler's waits
+            // in the loop below vmcnt(0), it cannot order it against the others — see the note in `stream`)
+            __builtin_amdgcn_s_waitcnt(0x0070); // vmcnt(0) lgkmcnt(0)
+            uint64_t w[SD][TU];
+            int64_t b0 = base + stride; // tile in slot 0
+#pragma unroll
+            for (int d = 0; d < SD; ++d) load_test(w[d], b0 + d * stride);
+            for (;;) {
+                int first = SD; // first slot whose tile has a passing row (wave-uniform)
+#pragma unroll
+                for (int d = 0; d < SD; ++d) {
+                    const bool h = test_hit(w[d], b0 + d * stride);
+                    first = (first == SD && h) ? d : first;
+                    load_test(w[d], b0 + (d + SD) * stride);
+                    __builtin_amdgcn_sched_barrier(0); // (the scheduler would gather all of the pass's requests in front of one vmcnt(0))
+                }
+                if (first < SD || b0 + SD * stride >= n) {
+                    base = b0 + first * stride; // (no hit: the first tile past the end)
+                    break;
+                }
+                b0 += SD * stride;
+            }
+            // (the words still in flight are dropped; waiting for them here keeps the row loops' waits what they were without this loop)
+            __builtin_amdgcn_s_waitcnt(0x0070);
+            if (base < n) load_tile(A, base);
+        }
+    };
+    // up to 2 x `budget` tiles.  In: A holds tile `base` (< n).  Out: base >= n (done or abandoned), or A holds tile `base` (SKIP:
+    // `miss` set — no row of the wave passed in the tile before it).
     auto stream = [&](auto &&process, Tile &A, int budget) {
         if constexpr (!PIPE) {
             for (int64_t it = 0; it < 2 * int64_t(budget); ++it) {
@@ -549,13 +637,22 @@ __global__ void __launch_bounds__(AGG_BLOCK) agg_grouped_fast_kernel(AggArgs a, 
         Tile B;
         for (int it = 0; it < budget; ++it) {
             load_tile(B, base + stride); // prefetch (clamped, always issued)
-            process(A, base);
+            const bool hit_a = process(A, base);
             base += stride;
             if (base >= n) return;
+            if (SKIP && !hit_a) { // no row of the wave passed: the key-only loop takes over from the tile in hand
+                A = B;
+                miss = true;
+                return;
+            }
             load_tile(A, base + stride);
-            process(B, base);
+            const bool hit_b = process(B, base);
             base += stride;
             if (base >= n) return;
+            if (SKIP && !hit_b) {
+                miss = true;
+                return;
+            }
             // (The flag loads below — a FLAT load of the LDS word and a device-scope load — are waited for with s_waitcnt vmcnt(0), i.e.
             // behind tile A's prefetch issued a moment ago, and the wave then sits with nothing in flight for a round trip to L2.  Looking
             // only every 8th iteration helps the one-tile loop above — three value columns 4.59 -> 4.42 ms, four A/B rounds — but not
@@ -581,6 +678,11 @@ __global__ void __launch_bounds__(AGG_BLOCK) agg_grouped_fast_kernel(AggArgs a, 
         constexpr bool CAN_BATCH = NQE_AGG_BATCH && !VNULL && PRED != 3 && (PRED != 6 && (PRED != 5 || (NQE_AGG_BATCH_TREE && KEY != 3 && NVT == 1))) && !(PRED == 2 && KEY == 3) && !(PRED == 4 && KEY == 3) &&
                                    (NVT == 1 || ((NQE_AGG_BATCH2 || !MM || ML) && KEY != 3 && PRED != 4));
         while (base < n) {
+            if (SKIP && miss) {
+                miss = false;
+                skip_tiles(A);
+                continue;
+            }
             bool batch = false; // wave-uniform
             if (CAN_BATCH) {
                 uint64_t key[TU];
