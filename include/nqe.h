@@ -517,6 +517,22 @@ nqe_status nqe_hash_join_probe(nqe_ctx *ctx, const nqe_join_table *build, const 
                                int32_t right_key, nqe_table **out);
 nqe_status nqe_join_table_release(nqe_join_table *jt);
 
+/* ------------------------------------------------------------------ cross join
+ * CrossJoin::execute (cross_join.rs:55-185) for one outer (left) batch and one inner (right)
+ * batch; the caller loops over the batch pairs outer-major, one output batch per pair, and a side
+ * without batches gives no output batches.  Quirk Q15: with L = left rows and R = right rows the
+ * output has N = L*R rows, left columns first, then right columns; output row j takes left row
+ * j % L and right row j % R (the reference's loop order: a Cartesian product only when
+ * gcd(L, R) = 1).  Validity is dropped: Int64/UInt64/Float64 outputs hold the raw 8-byte slots,
+ * Utf8 outputs the bytes between a slot's offsets, also under a NULL; no output has a validity
+ * bitmap (null_count 0).  join_type is ignored and nothing is kept between calls.
+ * Errors, decided on the host before anything is allocated or launched: a Boolean column on either
+ * side NQE_ERR_NOT_SUPPORTED, also at 0 rows (the reference panics: unimplemented!()); a Utf8 output
+ * of more than INT32_MAX bytes NQE_ERR_NOT_SUPPORTED (its int32 offsets overflow: the reference
+ * panics); L*R or a column's byte size beyond int64, or an output larger than the device,
+ * NQE_ERR_OUT_OF_MEMORY. */
+nqe_status nqe_cross_join_execute(nqe_ctx *ctx, const nqe_table *left, const nqe_table *right, nqe_table **out);
+
 /* ------------------------------------------------------------------ take
  * arrow::compute::take(array, &Int64Array indices, None) over every column
  * (hash_join.rs:239,245): out[j] = in[indices[j]]; `indices` = Int64 column `idx_column` of

@@ -21,7 +21,7 @@
 //!   3. `src/datasource/mod.rs:17`:      one more method on `trait TableSource`:
 //!          `fn scan_device(&self, _projection: Option<Vec<usize>>) -> Option<Result<Vec<crate::physical_plan::GpuBatch>>> { None }`
 //!   4. `pub(crate)` on the fields of `ScanPlan` (scan.rs:19-22), `SelectionPlan` (selection.rs:23-27), `ProjectionPlan`
-//!      (projection.rs:18-23), `HashJoin::{left,right,on,schema}` (hash_join.rs:44-56), `PhysicalLimitPlan` (limit.rs:15-19),
+//!      (projection.rs:18-23), `HashJoin::{left,right,on,schema}` (hash_join.rs:44-56), `CrossJoin::{left,right,schema}` (cross_join.rs:26-32), `PhysicalLimitPlan` (limit.rs:15-19),
 //!      `PhysicalOffsetPlan` (offset.rs:15-19) and `PhysicalBinaryExpr` (expression/binary.rs:91-96).
 //!   5. `src/physical_plan/aggregate/mod.rs:225`: one more method on `trait AggregateOperator`, one line in each of
 //!      sum.rs / avg.rs / count.rs / max.rs / min.rs:
@@ -50,7 +50,7 @@ use crate::error::{ErrorCode, Result};
 use crate::logical_plan::expression::{AggregateFunc, Column, ScalarValue};
 use crate::logical_plan::schema::NaiveSchema;
 use crate::physical_plan::{
-    ColumnExpr, HashJoin, PhysicalAggregatePlan, PhysicalBinaryExpr, PhysicalExprRef, PhysicalLimitPlan, PhysicalLiteralExpr, PhysicalOffsetPlan,
+    ColumnExpr, CrossJoin, HashJoin, PhysicalAggregatePlan, PhysicalBinaryExpr, PhysicalExprRef, PhysicalLimitPlan, PhysicalLiteralExpr, PhysicalOffsetPlan,
     PhysicalPlan, PhysicalPlanRef, ProjectionPlan, ScanPlan, SelectionPlan,
 };
 
@@ -98,6 +98,7 @@ extern "C" {
     fn nqe_hash_join_build(ctx: *mut NqeCtx, left: *const NqeTable, left_key: i32, out: *mut *mut NqeJoinTable) -> i32;
     fn nqe_hash_join_probe(ctx: *mut NqeCtx, build: *const NqeJoinTable, right: *const NqeTable, right_key: i32, out: *mut *mut NqeTable) -> i32;
     fn nqe_join_table_release(jt: *mut NqeJoinTable) -> i32;
+    fn nqe_cross_join_execute(ctx: *mut NqeCtx, left: *const NqeTable, right: *const NqeTable, out: *mut *mut NqeTable) -> i32;
 }
 
 // ------------------------------------------------------------------ context, device tables, upload, download
@@ -561,6 +562,38 @@ impl PhysicalPlan for GpuHashJoin {
     fn as_gpu(&self) -> Option<&dyn GpuExec> { Some(self) }
 }
 
+/// CrossJoin (cross_join.rs:26-192): one output batch per (outer, inner) batch pair, outer-major; quirk Q15: output row j takes left
+/// row j % L and right row j % R, no validity bitmaps; `join_type` is not read and nothing is kept between executions
+#[derive(Debug)]
+pub struct GpuCrossJoin { left: PhysicalPlanRef, right: PhysicalPlanRef, schema: NaiveSchema, ctx: Arc<GpuCtx> }
+impl GpuCrossJoin {
+    pub fn create(ctx: Arc<GpuCtx>, left: PhysicalPlanRef, right: PhysicalPlanRef, schema: NaiveSchema) -> PhysicalPlanRef {
+        Arc::new(Self { left, right, schema, ctx })
+    }
+}
+impl GpuExec for GpuCrossJoin {
+    fn execute_device(&self) -> Result<Vec<GpuBatch>> {
+        let outer = child_device(&self.ctx, &self.left)?;
+        let inner = child_device(&self.ctx, &self.right)?;
+        let mut out = vec![];
+        for o in &outer { // cross_join.rs:63-64
+            for i in &inner {
+                let mut t = std::ptr::null_mut();
+                self.ctx.check(unsafe { nqe_cross_join_execute(self.ctx.0, o.table.0, i.table.0, &mut t) })?;
+                out.push(GpuBatch::wrap(t));
+            }
+        }
+        Ok(out)
+    }
+}
+impl PhysicalPlan for GpuCrossJoin {
+    fn schema(&self) -> &NaiveSchema { &self.schema }
+    fn children(&self) -> Result<Vec<PhysicalPlanRef>> { Ok(vec![self.left.clone(), self.right.clone()]) }
+    fn execute(&self) -> Result<Vec<RecordBatch>> { self.ctx.download_all(&self.execute_device()?, &self.schema) }
+    fn as_any(&self) -> &dyn Any { self }
+    fn as_gpu(&self) -> Option<&dyn GpuExec> { Some(self) }
+}
+
 /// PhysicalLimitPlan / PhysicalOffsetPlan (limit.rs:32-49, offset.rs:30-51) over device batches: whole batches are passed on,
 /// a cut batch is nqe_table_slice — so a LIMIT above a device operator downloads `n` rows, not the operator's whole result
 #[derive(Debug)]
@@ -624,8 +657,8 @@ impl GpuCtx {
 // ------------------------------------------------------------------ the rewrite pass (what rewrite.py / naive_db.hpp `rewrite` do)
 // The planner keeps building the plain tree (planner/mod.rs:42-182); this pass (db.rs:34-36, between create_physical_plan and
 // execute: patch item 6) substitutes the device operators bottom-up, fusing Projection∘Selection and Aggregate∘Selection.
-// An operator it does not know (CrossJoin, NestedLoopJoin) is left as it is, children included: its `execute()` pulls host
-// batches from whatever is below.
+// A CrossJoin becomes GpuCrossJoin on one device; on a rank of a sharded deployment (`comm`) it is left as it is, like an operator
+// the pass does not know (NestedLoopJoin): children included, its `execute()` pulls host batches from whatever is below.
 pub fn rewrite(ctx: &Arc<GpuCtx>, plan: PhysicalPlanRef) -> Result<PhysicalPlanRef> { rewrite_sharded(ctx, None, plan) }
 /// the same pass for one rank of a multi-GPU deployment (`comm`: aggregates merge over the ranks, joins return this rank's rows)
 pub fn rewrite_sharded(ctx: &Arc<GpuCtx>, comm: Option<&Arc<GpuComm>>, plan: PhysicalPlanRef) -> Result<PhysicalPlanRef> {
@@ -656,6 +689,11 @@ pub fn rewrite_sharded(ctx: &Arc<GpuCtx>, comm: Option<&Arc<GpuComm>>, plan: Phy
     if let Some(j) = any.downcast_ref::<HashJoin>() {
         return Ok(GpuHashJoin::create(ctx.clone(), rewrite(ctx, j.left.clone())?, rewrite(ctx, j.right.clone())?, j.on.clone(), j.schema.clone(),
                                       comm.map(|c| (c.clone(), false))));
+    }
+    if let Some(c) = any.downcast_ref::<CrossJoin>() {
+        if comm.is_none() {
+            return Ok(GpuCrossJoin::create(ctx.clone(), rewrite(ctx, c.left.clone())?, rewrite(ctx, c.right.clone())?, c.schema.clone()));
+        }
     }
     if let Some(l) = any.downcast_ref::<PhysicalLimitPlan>() {
         return Ok(GpuLimitPlan::create_limit(ctx.clone(), rewrite(ctx, l.input.clone())?, l.n));

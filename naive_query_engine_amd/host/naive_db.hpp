@@ -621,6 +621,40 @@ struct HashJoin : PhysicalPlan {
     }
 };
 
+// ---------------------------------------------------------------- physical_plan/cross_join.rs:26-192
+// One output batch per (outer, inner) batch pair, outer-major.  Quirk Q15: output row j takes left row j % L and right row j % R
+// (a Cartesian product only when gcd(L, R) = 1); no output column has a validity bitmap; nothing is kept between execute() calls.
+struct CrossJoin : PhysicalPlan {
+    PhysicalPlanRef left, right;
+    JoinType join_type = JoinType::Cross; // stored, never read
+    NaiveSchema schema_;
+    static PhysicalPlanRef create(PhysicalPlanRef left, PhysicalPlanRef right, JoinType jt, NaiveSchema schema) {
+        auto p = std::make_shared<CrossJoin>();
+        p->left = std::move(left); p->right = std::move(right); p->join_type = jt; p->schema_ = std::move(schema);
+        return p;
+    }
+    const NaiveSchema &schema() const override { return schema_; }
+    std::vector<PhysicalPlanRef> children() const override { return {left, right}; }
+    std::vector<RecordBatch> execute() override {
+        std::vector<RecordBatch> outer = left->execute(), inner = right->execute();
+        std::vector<RecordBatch> out;
+        for (auto &o : outer) { // cross_join.rs:63-64
+            for (auto &i : inner) {
+                nqe_table *t = nullptr;
+                o.ctx()->check(nqe_cross_join_execute(o.ctx()->raw(), o.raw(), i.raw(), &t));
+                NaiveSchema s = schema_;
+                if (int32_t(s.fields().size()) != nqe_table_num_columns(t)) {
+                    std::vector<NaiveField> f = o.schema().fields();
+                    for (auto &x : i.schema().fields()) f.push_back(x);
+                    s = NaiveSchema(f);
+                }
+                out.push_back(o.with_table(s, t));
+            }
+        }
+        return out;
+    }
+};
+
 // ---------------------------------------------------------------- physical_plan/visitor.rs:4-24
 struct PhysicalPlanVisitor { // trait PhysicalPlanVistor
     virtual ~PhysicalPlanVisitor() = default;
@@ -726,6 +760,7 @@ inline PhysicalPlanRef rewrite(const PhysicalPlanRef &plan) {
     if (auto l = std::dynamic_pointer_cast<PhysicalLimitPlan>(plan)) return PhysicalLimitPlan::create(rewrite(l->input), l->n);
     if (auto o = std::dynamic_pointer_cast<PhysicalOffsetPlan>(plan)) return PhysicalOffsetPlan::create(rewrite(o->input), o->n);
     if (auto j = std::dynamic_pointer_cast<HashJoin>(plan)) return HashJoin::create(rewrite(j->left), rewrite(j->right), j->on, j->join_type, j->schema_);
+    if (auto c = std::dynamic_pointer_cast<CrossJoin>(plan)) return CrossJoin::create(rewrite(c->left), rewrite(c->right), c->join_type, c->schema_);
     return plan; // scans, fused operators, operators this pass does not know
 }
 

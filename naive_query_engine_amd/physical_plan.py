@@ -462,3 +462,34 @@ class HashJoin(PhysicalPlan):
             fields = self._schema if len(self._schema) == t.num_columns else list(lb[0].fields) + list(b.fields)
             out.append(DeviceRecordBatch(fields, t))
         return out
+
+
+# ----------------------------------------------------------------------------- cross join
+class CrossJoin(PhysicalPlan):
+    """src/physical_plan/cross_join.rs:26-192 — one output batch per (outer, inner) batch pair, outer-major; quirk Q15: with L and R
+    the pair's row counts, output row j takes left row j % L and right row j % R (a Cartesian product only when gcd(L, R) = 1), and
+    no output column has a validity bitmap.  `join_type` is stored and never read; nothing is kept between execute() calls."""
+
+    def __init__(self, left, right, join_type, schema):
+        self.left, self.right, self.join_type, self._schema = left, right, join_type, list(schema)
+
+    @staticmethod
+    def create(left: PhysicalPlan, right: PhysicalPlan, join_type, schema: NaiveSchema) -> "CrossJoin":
+        return CrossJoin(left, right, join_type, schema)
+
+    def schema(self):
+        return self._schema
+
+    def children(self):
+        return [self.left, self.right]
+
+    def execute(self):
+        outer = self.left.execute()
+        inner = self.right.execute()
+        out = []
+        for o in outer:  # cross_join.rs:63-64
+            for i in inner:
+                t = o.table.ctx.cross_join(o.table, i.table)
+                fields = self._schema if len(self._schema) == t.num_columns else list(o.fields) + list(i.fields)
+                out.append(DeviceRecordBatch(fields, t))
+        return out
