@@ -118,9 +118,12 @@ typedef struct nqe_column {
  * resolves names to the first matching index, planner/mod.rs:190-200),
  * PhysicalLiteralExpr(ScalarValue) (expression/literal.rs:17-26,
  * logical_plan/expression.rs:174-187) and PhysicalBinaryExpr(l, Operator, r)
- * (expression/binary.rs:91-101). A tree is valid when evaluating the nodes
- * left-to-right on a stack leaves exactly one value. */
-typedef enum nqe_expr_kind { NQE_EXPR_COLUMN = 0, NQE_EXPR_LITERAL = 1, NQE_EXPR_BINARY = 2 } nqe_expr_kind;
+ * (expression/binary.rs:91-101), and PhysicalUnaryExpr(expr, UnaryOperator, name, return_type)
+ * (expression/unary.rs:46-78; `name` and `return_type` are ignored by evaluate and have no
+ * place in the encoding). A BINARY node pops two operands (right on top), a UNARY node pops
+ * one; each pushes its result. A tree is valid when evaluating the nodes left-to-right on a
+ * stack leaves exactly one value. */
+typedef enum nqe_expr_kind { NQE_EXPR_COLUMN = 0, NQE_EXPR_LITERAL = 1, NQE_EXPR_BINARY = 2, NQE_EXPR_UNARY = 3 } nqe_expr_kind;
 
 /* same order as `enum Operator` (logical_plan/expression.rs:335-362) */
 typedef enum nqe_operator {
@@ -139,9 +142,30 @@ typedef enum nqe_operator {
     NQE_OP_OR = 12
 } nqe_operator;
 
+/* same order as `enum UnaryOperator` (logical_plan/expression.rs:392-422). Only the four math
+ * functions have a body in the reference (unary.rs:92-107), and only over Float64; quirk Q16:
+ * TAN evaluates the COSINE (unary.rs:96). The string functions are todo!() there and
+ * NQE_ERR_NOT_SUPPORTED here. */
+typedef enum nqe_unary_operator {
+    NQE_UNARY_ABS = 0,
+    NQE_UNARY_SIN = 1,
+    NQE_UNARY_COS = 2,
+    NQE_UNARY_TAN = 3,
+    NQE_UNARY_TRIM = 4,
+    NQE_UNARY_LTRIM = 5,
+    NQE_UNARY_RTRIM = 6,
+    NQE_UNARY_CHARACTER_LENGTH = 7,
+    NQE_UNARY_LOWER = 8,
+    NQE_UNARY_UPPER = 9,
+    NQE_UNARY_REPEAT = 10,
+    NQE_UNARY_REPLACE = 11,
+    NQE_UNARY_REVERSE = 12,
+    NQE_UNARY_SUBSTR = 13
+} nqe_unary_operator;
+
 typedef struct nqe_expr_node {
     int32_t kind;    /* nqe_expr_kind */
-    int32_t op;      /* BINARY: nqe_operator */
+    int32_t op;      /* BINARY: nqe_operator; UNARY: nqe_unary_operator */
     int32_t column;  /* COLUMN: index into the input batch */
     int32_t dtype;   /* LITERAL: nqe_dtype of the ScalarValue */
     int32_t is_null; /* LITERAL: 1 = ScalarValue::X(None) */
@@ -421,9 +445,18 @@ nqe_status nqe_sharded_selection_projection_execute(nqe_comm *comm, const nqe_ta
  * except a root literal, which is expanded to `in.num_rows` rows as into_array does.
  * Compares (= != < <= > >=) work on every type incl. Utf8 (byte-wise lexicographic, as arrow's
  * *_dyn kernels); and/or are Kleene; arithmetic is wrapping on Int64/UInt64, IEEE on Float64.
- * A tree of binary nodes is evaluated in one pass over the columns it references.
+ * Unary nodes (unary.rs:85-108): abs / sin / cos / tan over a Float64 operand give Float64 with
+ * the operand's validity (a column operand's validity buffer is shared, not copied; slots under
+ * a NULL are unspecified); a literal operand is expanded to `in.num_rows` rows. abs clears the
+ * sign bit and nothing else (-0.0 → 0.0, a NaN keeps its payload); sin / cos are the device
+ * math library's double-precision functions (OpenCL full profile: 4 ulp); tan is the cosine
+ * (quirk Q16).
+ * A tree of binary and unary nodes is evaluated in one pass over the columns it references.
  * Errors: operand dtype mismatch → NQE_ERR_INTERVAL; divide/modulus with a valid zero
- * divisor → NQE_ERR_ARROW; arithmetic on Boolean/Utf8 → NQE_ERR_NOT_SUPPORTED. */
+ * divisor → NQE_ERR_ARROW; arithmetic on Boolean/Utf8 → NQE_ERR_NOT_SUPPORTED; a unary node
+ * over anything but Float64 or any of the string functions → NQE_ERR_NOT_SUPPORTED; a unary
+ * node without an operand or with an `op` outside nqe_unary_operator →
+ * NQE_ERR_INVALID_ARGUMENT. All of these are decided before anything is allocated or launched. */
 nqe_status nqe_expr_evaluate(nqe_ctx *ctx, const nqe_table *in, const nqe_expr_node *nodes,
                              int32_t num_nodes, nqe_table **out);
 

@@ -22,7 +22,8 @@
 //!          `fn scan_device(&self, _projection: Option<Vec<usize>>) -> Option<Result<Vec<crate::physical_plan::GpuBatch>>> { None }`
 //!   4. `pub(crate)` on the fields of `ScanPlan` (scan.rs:19-22), `SelectionPlan` (selection.rs:23-27), `ProjectionPlan`
 //!      (projection.rs:18-23), `HashJoin::{left,right,on,schema}` (hash_join.rs:44-56), `CrossJoin::{left,right,schema}` (cross_join.rs:26-32), `PhysicalLimitPlan` (limit.rs:15-19),
-//!      `PhysicalOffsetPlan` (offset.rs:15-19) and `PhysicalBinaryExpr` (expression/binary.rs:91-96).
+//!      `PhysicalOffsetPlan` (offset.rs:15-19), `PhysicalBinaryExpr` (expression/binary.rs:91-96) and `PhysicalUnaryExpr::{expr,func}`
+//!      (expression/unary.rs:46-51).
 //!   5. `src/physical_plan/aggregate/mod.rs:225`: one more method on `trait AggregateOperator`, one line in each of
 //!      sum.rs / avg.rs / count.rs / max.rs / min.rs:
 //!          `fn describe(&self) -> (AggregateFunc, ColumnExpr);`             (e.g. `(AggregateFunc::Sum, self.col_expr.clone())`)
@@ -51,7 +52,7 @@ use crate::logical_plan::expression::{AggregateFunc, Column, ScalarValue};
 use crate::logical_plan::schema::NaiveSchema;
 use crate::physical_plan::{
     ColumnExpr, CrossJoin, HashJoin, PhysicalAggregatePlan, PhysicalBinaryExpr, PhysicalExprRef, PhysicalLimitPlan, PhysicalLiteralExpr, PhysicalOffsetPlan,
-    PhysicalPlan, PhysicalPlanRef, ProjectionPlan, ScanPlan, SelectionPlan,
+    PhysicalPlan, PhysicalPlanRef, PhysicalUnaryExpr, ProjectionPlan, ScanPlan, SelectionPlan,
 };
 
 // ------------------------------------------------------------------ FFI (1:1 with include/nqe.h)
@@ -71,6 +72,9 @@ pub enum NqeTable {}
 pub enum NqeJoinTable {}
 pub enum NqeComm {}
 
+// nqe_expr_kind; nqe_unary_operator is `enum UnaryOperator` in declaration order (expression.rs:392-422): Abs = 0, Sin = 1, Cos = 2, Tan = 3,
+// Trim = 4, LTrim = 5, RTrim = 6, CharacterLength = 7, Lower = 8, Upper = 9, Repeat = 10, Replace = 11, Reverse = 12, Substr = 13
+const NQE_EXPR_COLUMN: i32 = 0; const NQE_EXPR_LITERAL: i32 = 1; const NQE_EXPR_BINARY: i32 = 2; const NQE_EXPR_UNARY: i32 = 3;
 const NQE_BOOLEAN: i32 = 1; const NQE_INT64: i32 = 2; const NQE_UINT64: i32 = 3; const NQE_FLOAT64: i32 = 4; const NQE_UTF8: i32 = 5;
 
 extern "C" {
@@ -317,9 +321,9 @@ fn resolve(c: &ColumnExpr, schema: &NaiveSchema) -> Result<i32> {
 /// `keep` holds the bytes of Utf8 literals for the duration of the call (the ABI borrows them)
 fn flatten(e: &PhysicalExprRef, schema: &NaiveSchema, out: &mut Vec<NqeExprNode>, keep: &mut Vec<Vec<u8>>) -> Result<()> {
     if let Some(c) = e.as_any().downcast_ref::<ColumnExpr>() {
-        out.push(NqeExprNode { kind: 0, column: resolve(c, schema)?, ..zero_node() });
+        out.push(NqeExprNode { kind: NQE_EXPR_COLUMN, column: resolve(c, schema)?, ..zero_node() });
     } else if let Some(l) = e.as_any().downcast_ref::<PhysicalLiteralExpr>() {
-        let mut n = NqeExprNode { kind: 1, ..zero_node() };
+        let mut n = NqeExprNode { kind: NQE_EXPR_LITERAL, ..zero_node() };
         match &l.literal {
             ScalarValue::Null => { n.dtype = 0; n.is_null = 1; }
             ScalarValue::Boolean(v) => { n.dtype = NQE_BOOLEAN; n.is_null = v.is_none() as i32; n.value.boolean = v.unwrap_or(false) as i64; }
@@ -340,9 +344,14 @@ fn flatten(e: &PhysicalExprRef, schema: &NaiveSchema, out: &mut Vec<NqeExprNode>
     } else if let Some(b) = e.as_any().downcast_ref::<PhysicalBinaryExpr>() {
         flatten(&b.left, schema, out, keep)?;
         flatten(&b.right, schema, out, keep)?;
-        out.push(NqeExprNode { kind: 2, op: b.op.clone() as i32, ..zero_node() }); // Operator is declared in nqe_operator's order (expression.rs:335-362)
+        out.push(NqeExprNode { kind: NQE_EXPR_BINARY, op: b.op.clone() as i32, ..zero_node() }); // Operator is declared in nqe_operator's order (expression.rs:335-362)
+    } else if let Some(u) = e.as_any().downcast_ref::<PhysicalUnaryExpr>() {
+        // name / return_type are ignored by the reference's evaluate (unary.rs:85-108) and have no place in the encoding; Tan is the
+        // cosine on the device as it is there (quirk Q16); the string functions come back as NotSupported from the library
+        flatten(&u.expr, schema, out, keep)?;
+        out.push(NqeExprNode { kind: NQE_EXPR_UNARY, op: u.func.clone() as i32, ..zero_node() }); // UnaryOperator is declared in nqe_unary_operator's order
     } else {
-        return Err(ErrorCode::NotSupported("expression kind has no device implementation (cast / unary)".to_string()));
+        return Err(ErrorCode::NotSupported("expression kind has no device implementation (cast)".to_string()));
     }
     Ok(())
 }

@@ -45,6 +45,26 @@ class Operator(enum.IntEnum):
     Or = 12
 
 
+class UnaryOperator(enum.IntEnum):
+    """enum UnaryOperator (src/logical_plan/expression.rs:392-422), same order = nqe_unary_operator.  Only Abs, Sin, Cos and Tan
+    have a body in the reference (unary.rs:92-107); Tan evaluates the cosine (quirk Q16)."""
+
+    Abs = 0
+    Sin = 1
+    Cos = 2
+    Tan = 3
+    Trim = 4
+    LTrim = 5
+    RTrim = 6
+    CharacterLength = 7
+    Lower = 8
+    Upper = 9
+    Repeat = 10
+    Replace = 11
+    Reverse = 12
+    Substr = 13
+
+
 class AggregateFunc(enum.IntEnum):
     """enum AggregateFunc (src/logical_plan/expression.rs:491-502), same order."""
 
@@ -130,7 +150,7 @@ class NqeCsvOptions(C.Structure):
     _fields_ = [("has_header", C.c_int32), ("delimiter", C.c_int32), ("max_read_records", C.c_int64), ("batch_size", C.c_int64)]
 
 
-EXPR_COLUMN, EXPR_LITERAL, EXPR_BINARY = 0, 1, 2
+EXPR_COLUMN, EXPR_LITERAL, EXPR_BINARY, EXPR_UNARY = 0, 1, 2, 3
 HOST, DEVICE = 0, 1
 
 _WORD_NP = {DType.INT64: np.int64, DType.UINT64: np.uint64, DType.FLOAT64: np.float64}
@@ -459,6 +479,13 @@ def node_binary(op: Operator) -> NqeExprNode:
     n = NqeExprNode()
     n.kind = EXPR_BINARY
     n.op = int(op)
+    return n
+
+
+def node_unary(func: "UnaryOperator") -> NqeExprNode:
+    n = NqeExprNode()
+    n.kind = EXPR_UNARY
+    n.op = int(func)
     return n
 
 

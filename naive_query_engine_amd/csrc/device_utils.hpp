@@ -139,6 +139,15 @@ __device__ __forceinline__ uint64_t apply_binary(int op, int dt, uint64_t a, uin
     return divmod_general(op, dt, a, b);
 }
 
+// One unary step on a raw Float64 word (unary.rs:92-96).  F is a compile-time nqe_unary_operator so that `abs` carries no
+// transcendental code.  Abs clears the sign bit and nothing else; Sin / Cos are the device library's double-precision functions
+// (the interpreter, the node kernel and the run-time generated kernels all call these same two); Tan is the COSINE (quirk Q16).
+template <int F> __device__ __forceinline__ uint64_t apply_unary(uint64_t w) {
+    if (F == NQE_UNARY_ABS) return w & 0x7fffffffffffffffull;
+    if (F == NQE_UNARY_SIN) return d2u(sin(u2d(w)));
+    return d2u(cos(u2d(w))); // NQE_UNARY_COS and NQE_UNARY_TAN (Q16)
+}
+
 __device__ __forceinline__ OpAux no_aux() {
     OpAux a;
     a.pow2_shift = -1;

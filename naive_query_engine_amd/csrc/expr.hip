@@ -1,10 +1,10 @@
 // expr.hip — PhysicalExpr::evaluate on the device (reference: src/physical_plan/expression/
-// binary.rs:108-155, column.rs:39-57, literal.rs:32-34; arrow-rs 13 compare / kleene /
-// arithmetic kernels at the call sites binary.rs:127-153).
+// binary.rs:108-155, unary.rs:85-108, column.rs:39-57, literal.rs:32-34; arrow-rs 13 compare /
+// kleene / arithmetic / arity::unary kernels at the call sites binary.rs:127-153, unary.rs:28-29).
 //
 // Two evaluation forms:
-//   * general: one streaming kernel per binary node (what arrow does), except that literals
-//     stay scalars in registers instead of being materialised as n-row columns
+//   * general: one streaming kernel per binary or unary node (what arrow does), except that
+//     literals stay scalars in registers instead of being materialised as n-row columns
 //     (logical_plan/expression.rs:210-222, the TODO at binary.rs:121);
 //   * fused:   `col [op lit]{0,2}` shapes (SimpleExpr) are evaluated inside the consumer
 //     kernel (compaction, aggregation) from the streamed word — no temporary at all.
@@ -23,15 +23,16 @@ struct Node {
     bool lit_null = false;
     uint64_t lit = 0;
     std::string lit_str;       // Utf8 literal
-    int left = -1, right = -1; // children (indices into the node vector)
+    int left = -1, right = -1; // children (indices into the node vector); a UNARY node's operand is `left`
     int out_dtype = NQE_NULLTYPE;
 };
 
 bool is_compare(int op) { return op >= NQE_OP_EQ && op <= NQE_OP_GT_EQ; }
 bool is_logic(int op) { return op == NQE_OP_AND || op == NQE_OP_OR; }
 bool is_arith(int op) { return op >= NQE_OP_PLUS && op <= NQE_OP_MODULOS; }
+bool is_op_node(int kind) { return kind == NQE_EXPR_BINARY || kind == NQE_EXPR_UNARY; } // a node with operands: a step of a program
 
-// builds the tree and type-checks it exactly where binary.rs does
+// builds the tree and type-checks it exactly where binary.rs and unary.rs do
 std::vector<Node> parse(const nqe_table *in, const nqe_expr_node *nodes, int n, int *root) {
     if (!nodes || n <= 0) fail(NQE_ERR_INVALID_ARGUMENT, "empty expression");
     std::vector<Node> t;
@@ -80,6 +81,15 @@ std::vector<Node> parse(const nqe_table *in, const nqe_expr_node *nodes, int n, 
             } else {
                 fail(NQE_ERR_INVALID_ARGUMENT, "unknown operator");
             }
+        } else if (nd.kind == NQE_EXPR_UNARY) { // unary.rs:85-108
+            if (st.empty()) fail(NQE_ERR_INVALID_ARGUMENT, "malformed expression");
+            x.left = st.back(); st.pop_back();
+            x.op = nd.op;
+            if (x.op < NQE_UNARY_ABS || x.op > NQE_UNARY_SUBSTR) fail(NQE_ERR_INVALID_ARGUMENT, "unknown unary operator");
+            if (x.op > NQE_UNARY_TAN) fail(NQE_ERR_NOT_SUPPORTED, "the string functions are todo!() (unary.rs:97-106)");
+            if (t[size_t(x.left)].out_dtype != NQE_FLOAT64) // unary_arith_op! `_ => unimplemented!()` (unary.rs:41)
+                fail(NQE_ERR_NOT_SUPPORTED, "unary math functions on this type are unimplemented!() (unary.rs:41)");
+            x.out_dtype = NQE_FLOAT64;
         } else {
             fail(NQE_ERR_INVALID_ARGUMENT, "unknown expression node kind");
         }
@@ -220,15 +230,37 @@ __global__ void __launch_bounds__(256) binary_kernel(Operand a, Operand b, int o
     }
 }
 
+// out = f(in) over Float64 words, one kernel per UNARY node of the node-at-a-time form (arity::unary, unary.rs:28-29): validity is
+// not touched (the output column shares the operand's bitmap), so NULL slots are mapped like any other.  Two rows per lane through
+// 16-byte accesses over the first `pairs` row pairs (the host passes 0 when either buffer is not 16-byte aligned), the rest one row
+// per lane (one load in flight per lane: more of them, or more waves per CU, measured slower — see the launch site).  F is a
+// template parameter: the abs instance is an `and` between a load and a store.
+typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
+template <int F>
+__global__ void __launch_bounds__(256) unary_f64_kernel(const uint64_t *__restrict__ in, uint64_t *__restrict__ out, int64_t pairs, int64_t n) {
+    const int64_t stride = int64_t(gridDim.x) * blockDim.x, first = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    const u64x2 *in2 = reinterpret_cast<const u64x2 *>(in);
+    u64x2 *out2 = reinterpret_cast<u64x2 *>(out);
+    for (int64_t j = first; j < pairs; j += stride) {
+        u64x2 v = __builtin_nontemporal_load(in2 + j);
+        v.x = apply_unary<F>(v.x);
+        v.y = apply_unary<F>(v.y);
+        __builtin_nontemporal_store(v, out2 + j);
+    }
+    for (int64_t j = 2 * pairs + first; j < n; j += stride) out[j] = apply_unary<F>(in[j]);
+}
+
 __global__ void fill_words_kernel(uint64_t *out, uint64_t v, int64_t n) {
     int64_t stride = int64_t(gridDim.x) * blockDim.x;
     for (int64_t j = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; j < n; j += stride) out[j] = v;
 }
 
 // ------------------------------------------------------------------ fused whole-tree evaluation
-// A tree of binary nodes is evaluated in ONE pass by a small stack machine: one instruction per BINARY node
-// (post-order), whose operands are a literal (SGPR broadcast), a pre-loaded column word, or the top of a register-
-// resident stack of intermediate results.  Control flow is wave-uniform (the program lives in the kernel arguments).
+// A tree of binary and unary nodes is evaluated in ONE pass by a small stack machine: one instruction per BINARY or
+// UNARY node (post-order), whose operands are a literal (SGPR broadcast), a pre-loaded column word, or the top of a
+// register-resident stack of intermediate results.  A unary instruction (op = EX_OP_UNARY + nqe_unary_operator, b_src =
+// EX_NONE) has the one operand a_src and replaces the top of the stack when that operand is the stack (depth unchanged),
+// or pushes (depth + 1).  Control flow is wave-uniform (the program lives in the kernel arguments).
 // Reads each referenced column once and writes the result once — no temporaries (the reference / arrow materialise one
 // full column per node plus one per literal).
 //
@@ -238,9 +270,10 @@ __global__ void fill_words_kernel(uint64_t *out, uint64_t v, int64_t n) {
 // the next instruction is fetched while the current one executes.  The stack keeps its top at level 0 by register moves:
 // `stack op x` (the common left-deep shape) moves nothing.
 constexpr int EX_MAX_INSTR = 16, EX_MAX_COLS = 4, EX_MAX_DEPTH = 3, EX_ROWS = 4;
-enum ExSrc : int32_t { EX_STACK = 0, EX_LIT = 1, EX_LIT_NULL = 2, EX_COL = 4 /* + slot */ };
+enum ExSrc : int32_t { EX_STACK = 0, EX_LIT = 1, EX_LIT_NULL = 2, EX_NONE = 3 /* b_src of a unary instruction */, EX_COL = 4 /* + slot */ };
+constexpr int32_t EX_OP_UNARY = 32; // ExInstr::op of a unary instruction: EX_OP_UNARY + nqe_unary_operator (above every nqe_operator)
 struct ExInstr {
-    int32_t op, dt;       // operator, operand dtype
+    int32_t op, dt;       // operator (binary: nqe_operator; unary: EX_OP_UNARY + nqe_unary_operator), operand dtype
     int32_t a_src, b_src; // ExSrc
     uint64_t lit_a, lit_b;
     OpAux aux;            // host-prepared divisor constants when b is a literal
@@ -343,7 +376,9 @@ __device__ __forceinline__ void ex_load(const ExProgram &P, int64_t row0, int64_
 }
 
 // Runs the program on the loaded rows; the result words are left in res[], the returned mask holds their validity.
-template <bool NULLS, int NC, int R = EX_ROWS>
+// TRIG = false: the program holds no sin / cos step (the host checks), so that instance carries no transcendental code and
+// keeps the register budget of a purely arithmetic machine.
+template <bool NULLS, int NC, int R = EX_ROWS, bool TRIG = false>
 __device__ __forceinline__ uint32_t ex_run(const ExProgram &P, const uint64_t (&cw)[NC][R], const uint32_t (&cvm)[NC],
                                            uint32_t inm, uint32_t litm, uint64_t (&res)[R], int *flags) {
     // ---- run the program
@@ -423,7 +458,22 @@ __device__ __forceinline__ uint32_t ex_run(const ExProgram &P, const uint64_t (&
             for (int r = 0; r < R; ++r) b[r] = cw[NC > 2 ? 3 : 0][r];
         }
         uint32_t m;
-        if (cur.op == NQE_OP_AND || cur.op == NQE_OP_OR) {
+        if (cur.op >= EX_OP_UNARY) { // one operand (b is unused): the value is mapped, the validity passes through
+            m = NULLS ? am : inm;
+            const int f = cur.op - EX_OP_UNARY;
+            if (f == NQE_UNARY_ABS) {
+#pragma unroll
+                for (int r = 0; r < R; ++r) a[r] = apply_unary<NQE_UNARY_ABS>(a[r]);
+            } else if (TRIG) {
+                if (f == NQE_UNARY_SIN) {
+#pragma unroll
+                    for (int r = 0; r < R; ++r) a[r] = apply_unary<NQE_UNARY_SIN>(a[r]);
+                } else { // Cos, and Tan (quirk Q16)
+#pragma unroll
+                    for (int r = 0; r < R; ++r) a[r] = apply_unary<NQE_UNARY_COS>(a[r]);
+                }
+            }
+        } else if (cur.op == NQE_OP_AND || cur.op == NQE_OP_OR) {
             if (NULLS) { // and_kleene / or_kleene
                 m = 0;
 #pragma unroll
@@ -450,7 +500,7 @@ __device__ __forceinline__ uint32_t ex_run(const ExProgram &P, const uint64_t (&
                 for (int r = 0; r < R; ++r) a[r] = apply_binary(tag.op, tag.dt, a[r], b[r], cur.aux, (m >> r) & 1u, flags);
             });
         }
-        if (a_st && b_st) { // pop 2, push 1
+        if (a_st && b_st) { // pop 2, push 1 (a unary step over the stack: neither branch — the top is replaced in place)
             vm[1] = vm[2];
 #pragma unroll
             for (int r = 0; r < R; ++r) s[1][r] = s[2][r];
@@ -472,7 +522,7 @@ __device__ __forceinline__ uint32_t ex_run(const ExProgram &P, const uint64_t (&
 
 // R rows per lane: the dispatch of an instruction (scalar work) is paid once per R x 64 rows; 4 by default (8 halves the scalar work
 // but takes 176 VGPRs — see the launch site)
-template <bool NULLS, int NC, int R = EX_ROWS>
+template <bool NULLS, int NC, int R = EX_ROWS, bool TRIG = false>
 __global__ void __launch_bounds__(256) expr_tree_kernel(ExProgram P, int64_t n, uint64_t *out_words, uint64_t *out_bits, uint64_t *out_valid,
                                                         int *flags) {
     const int lane = lane_id();
@@ -486,7 +536,7 @@ __global__ void __launch_bounds__(256) expr_tree_kernel(ExProgram P, int64_t n, 
         uint64_t cw[NC][R], res[R];
         uint32_t cvm[NC];
         ex_load<NULLS, NC, R>(P, row0, n, inm, cw, cvm);
-        const uint32_t vm = ex_run<NULLS, NC, R>(P, cw, cvm, inm, inm, res, flags);
+        const uint32_t vm = ex_run<NULLS, NC, R, TRIG>(P, cw, cvm, inm, inm, res, flags);
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int64_t row = row0 + r * 64;
@@ -510,7 +560,7 @@ __global__ void __launch_bounds__(256) expr_tree_kernel(ExProgram P, int64_t n, 
 // compact_kernel); only the rows the filter emits are evaluated as valid (a dropped row can never raise DivideByZero,
 // as in the reference where the projection runs on the filtered batch), 256-row chunks without any kept row are not even
 // loaded, and results go straight to their compacted position.  A NULL predicate emits a NULL row (quirk Q4).
-template <bool NULLS, int NC>
+template <bool NULLS, int NC, bool TRIG = false>
 __global__ void __launch_bounds__(256) expr_tree_compact_kernel(ExProgram P, const uint64_t *keep, const uint64_t *pvalid,
                                                                 const uint64_t *tile_offsets, int64_t n, int64_t ntiles, uint64_t *out_words,
                                                                 uint8_t *out_bool_bytes, uint8_t *out_valid_bytes, int *flags) {
@@ -544,7 +594,7 @@ __global__ void __launch_bounds__(256) expr_tree_compact_kernel(ExProgram P, con
             uint64_t cw[NC][R], res[R];
             uint32_t cvm[NC];
             ex_load<NULLS, NC>(P, row0, n, inm, cw, cvm);
-            const uint32_t vm = ex_run<NULLS, NC>(P, cw, cvm, inm, litm, res, flags);
+            const uint32_t vm = ex_run<NULLS, NC, R, TRIG>(P, cw, cvm, inm, litm, res, flags);
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 if ((kw[r] >> lane) & 1ull) {
@@ -562,16 +612,17 @@ __global__ void __launch_bounds__(256) expr_tree_compact_kernel(ExProgram P, con
 // builds the stack program; false when the tree does not fit the machine (then: node-at-a-time)
 bool build_program(const nqe_table *in, const std::vector<Node> &t, int root, ExProgram *P, bool *needs_valid) {
     std::memset(P, 0, sizeof(*P));
-    std::vector<int> order; // BINARY nodes, post-order
+    if (getenv("NQE_NO_EXPR_TREE")) return false; // diagnostics (A/B, parity tests): every tree node-at-a-time
+    std::vector<int> order; // BINARY and UNARY nodes, post-order
     std::vector<std::pair<int, bool>> st = {{root, false}};
     while (!st.empty()) {
         auto [i, done] = st.back();
         st.pop_back();
         const Node &x = t[size_t(i)];
-        if (x.kind != NQE_EXPR_BINARY) continue;
+        if (!is_op_node(x.kind)) continue;
         if (done) { order.push_back(i); continue; }
         st.push_back({i, true});
-        st.push_back({x.right, false});
+        if (x.kind == NQE_EXPR_BINARY) st.push_back({x.right, false});
         st.push_back({x.left, false});
     }
     if (int(order.size()) > EX_MAX_INSTR || order.empty()) return false;
@@ -579,7 +630,7 @@ bool build_program(const nqe_table *in, const std::vector<Node> &t, int root, Ex
     bool fits = true;
     auto operand = [&](int idx, int32_t *src, uint64_t *lit) {
         const Node &x = t[size_t(idx)];
-        if (x.kind == NQE_EXPR_BINARY) { *src = EX_STACK; return; }
+        if (is_op_node(x.kind)) { *src = EX_STACK; return; }
         if (x.kind == NQE_EXPR_LITERAL) {
             if (x.dtype == NQE_UTF8) { fits = false; return; }
             *src = x.lit_null ? EX_LIT_NULL : EX_LIT;
@@ -606,10 +657,18 @@ bool build_program(const nqe_table *in, const std::vector<Node> &t, int root, Ex
     for (int i : order) {
         const Node &x = t[size_t(i)];
         ExInstr &I = P->ins[P->n++];
-        I.op = x.op;
         I.dt = t[size_t(x.left)].out_dtype;
         I.aux.pow2_shift = I.aux.more = -1;
         operand(x.left, &I.a_src, &I.lit_a);
+        if (x.kind == NQE_EXPR_UNARY) { // the one-operand form: replaces the top of the stack, or pushes
+            I.op = EX_OP_UNARY + x.op;
+            I.b_src = EX_NONE;
+            if (!fits) return false;
+            depth += 1 - int(I.a_src == EX_STACK);
+            if (depth > EX_MAX_DEPTH) return false;
+            continue;
+        }
+        I.op = x.op;
         operand(x.right, &I.b_src, &I.lit_b);
         if (!fits) return false;
         if (I.b_src == EX_LIT) I.aux = make_aux(x.op, I.dt, I.lit_b);
@@ -617,6 +676,13 @@ bool build_program(const nqe_table *in, const std::vector<Node> &t, int root, Ex
         if (depth > EX_MAX_DEPTH) return false;
     }
     return true;
+}
+
+// does the program hold a sin / cos step (the TRIG instances of the interpreting kernels)?
+bool program_has_trig(const ExProgram &P) {
+    for (int i = 0; i < P.n; ++i)
+        if (P.ins[i].op > EX_OP_UNARY + NQE_UNARY_ABS) return true;
+    return false;
 }
 
 struct Value {
@@ -671,6 +737,33 @@ Value eval_node(nqe_ctx *ctx, const nqe_table *in, const std::vector<Node> &t, i
         v.lit = x.lit;
         v.lit_str = x.lit_str;
         v.lit_null = x.lit_null;
+        return v;
+    }
+    if (x.kind == NQE_EXPR_UNARY) {
+        Value c = eval_node(ctx, in, t, x.left);
+        const int64_t n = in->rows;
+        if (c.is_lit) c.col = materialise_literal(ctx, c.dtype, c.lit, c.lit_null, n); // value.into_array() (unary.rs:90)
+        v.col = make_word_column(ctx, NQE_FLOAT64, n, false);
+        // arity::unary keeps the operand's null buffer: shared with the operand (reference-counted), unless it is memory borrowed
+        // from the caller, which an output may not alias
+        if (c.col.validity && !buf_shareable(c.col.validity)) {
+            v.col.validity = dev_alloc_zero(ctx, bitmap_alloc_bytes(n));
+            if (n) bitmap_place(ctx, c.col.valid(), (uint64_t *)v.col.validity->ptr, 0, n);
+        } else
+            v.col.validity = c.col.validity;
+        v.col.null_count = c.col.null_count;
+        if (n) {
+            const uint64_t *src = (const uint64_t *)c.col.values->ptr;
+            uint64_t *dst = (uint64_t *)v.col.values->ptr;
+            const int64_t pairs = ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) ? 0 : n / 2;
+            // four workgroups per CU, not the eight of the other streaming kernels: with 16 bytes per lane and access the same map over 10^8
+            // rows took 0.297 ms at 8 per CU, 0.311 at 16, 0.266 at 4 (abs, sin and `* 2.0` alike; two or four loads in flight per lane:
+            // 0.33 / 0.355; the stack machine's 4 x 8-byte pattern: 0.276) — tools/unary_kernel_bench.hip, profiles/unary/kernel_variants.txt
+            const dim3 grid(stream_grid(ctx, (n + 1) / 2, 256, 4));
+            if (x.op == NQE_UNARY_ABS) launch(ctx, "expr_unary", unary_f64_kernel<NQE_UNARY_ABS>, grid, dim3(256), 0, src, dst, pairs, n);
+            else if (x.op == NQE_UNARY_SIN) launch(ctx, "expr_unary", unary_f64_kernel<NQE_UNARY_SIN>, grid, dim3(256), 0, src, dst, pairs, n);
+            else launch(ctx, "expr_unary", unary_f64_kernel<NQE_UNARY_COS>, grid, dim3(256), 0, src, dst, pairs, n); // Cos, and Tan (quirk Q16, unary.rs:96)
+        }
         return v;
     }
     Value l = eval_node(ctx, in, t, x.left);
@@ -767,6 +860,7 @@ bool match_conj(const nqe_table *in, const nqe_expr_node *nodes, int n, ConjPred
     // first node of the subtree that ends at node i
     int start[MAXN], stack[MAXN], sp = 0;
     for (int i = 0; i < n; ++i) {
+        if (nodes[i].kind == NQE_EXPR_UNARY) return false; // (a test is `col [arith lit] cmp lit`: no one-operand step; such trees go through expr_tree_kernel)
         if (nodes[i].kind == NQE_EXPR_BINARY) {
             if (sp < 2) return false;
             sp -= 2;
@@ -898,6 +992,7 @@ bool match_tree_pred(const nqe_table *in, const nqe_expr_node *nodes, int n, Tre
     for (int i = 0; i < P.n; ++i) {
         const ExInstr &I = P.ins[i];
         if (I.a_src == EX_LIT_NULL || I.b_src == EX_LIT_NULL) return false;
+        if (I.op >= EX_OP_UNARY) return false; // (TreeInstr has no one-operand form: the predicate goes through expr_tree_kernel)
         TreeInstr &T = out->ins[i];
         T.op = I.op;
         T.dt = I.dt;
@@ -985,7 +1080,10 @@ DevColumn evaluate_expr(nqe_ctx *ctx, const nqe_table *in, const nqe_expr_node *
     std::vector<Node> t = parse(in, nodes, n, &root);
     ExProgram P;
     bool needs_valid = false;
-    if (t[size_t(root)].kind == NQE_EXPR_BINARY && build_program(in, t, root, &P, &needs_valid)) {
+    // f(column) / f(literal) alone is one pass in its node kernel as well, and there the result shares the column's validity buffer
+    const Node &rt = t[size_t(root)];
+    const bool bare_unary = rt.kind == NQE_EXPR_UNARY && !is_op_node(t[size_t(rt.left)].kind);
+    if (is_op_node(rt.kind) && !bare_unary && build_program(in, t, root, &P, &needs_valid)) {
         const int64_t rows = in->rows;
         const int odt = t[size_t(root)].out_dtype;
         const bool bool_out = odt == NQE_BOOLEAN;
@@ -995,7 +1093,12 @@ DevColumn evaluate_expr(nqe_ctx *ctx, const nqe_table *in, const nqe_expr_node *
             uint64_t *ow = bool_out ? nullptr : (uint64_t *)out.values->ptr, *ob = bool_out ? (uint64_t *)out.values->ptr : nullptr;
             uint64_t *ov = needs_valid ? (uint64_t *)out.validity->ptr : nullptr;
             // instantiated per (nullable, <=2 / <=4 columns): the column registers of a lane are the largest block of VGPRs
-#define NQE_TREE(NU, NC) launch(ctx, "expr_tree", expr_tree_kernel<NU, NC>, grid, dim3(256), 0, P, rows, ow, ob, ov, ctx->d_flags)
+            const bool trig = program_has_trig(P);
+#define NQE_TREE(NU, NC)                                                                                                                        \
+    do {                                                                                                                                        \
+        if (trig) launch(ctx, "expr_tree", expr_tree_kernel<NU, NC, EX_ROWS, true>, grid, dim3(256), 0, P, rows, ow, ob, ov, ctx->d_flags);       \
+        else launch(ctx, "expr_tree", expr_tree_kernel<NU, NC, EX_ROWS, false>, grid, dim3(256), 0, P, rows, ow, ob, ov, ctx->d_flags);           \
+    } while (0)
             // (8 rows per lane measured 176 VGPRs = 2 waves per SIMD — an 8-operator chain 1.19 -> 1.13 ms per 2x10^8 rows, but
             // `(id % 1000) * 3 + id / 7` 1.11 -> 1.36 and `v > 50 and id % 3 = 0` 0.98 -> 1.19: four rows per lane it is)
             // three or more steps over a large input: the run-time specialised form of this very program, once it has been compiled
@@ -1019,7 +1122,7 @@ bool evaluate_expr_compacted(nqe_ctx *ctx, const nqe_table *in, const nqe_expr_n
     std::vector<Node> t = parse(in, nodes, n, &root);
     ExProgram P;
     bool needs_valid = false;
-    if (t[size_t(root)].kind != NQE_EXPR_BINARY || !build_program(in, t, root, &P, &needs_valid)) return false;
+    if (!is_op_node(t[size_t(root)].kind) || !build_program(in, t, root, &P, &needs_valid)) return false;
     needs_valid |= km.pvalid != nullptr;
     const int64_t m = km.total;
     const int odt = t[size_t(root)].out_dtype;
@@ -1034,7 +1137,12 @@ bool evaluate_expr_compacted(nqe_ctx *ctx, const nqe_table *in, const nqe_expr_n
         const uint64_t *to = (const uint64_t *)km.tile_offsets->ptr;
         uint64_t *ow = bool_out ? nullptr : (uint64_t *)out.values->ptr;
         uint8_t *ob = bool_out ? (uint8_t *)bool_bytes->ptr : nullptr, *ov = needs_valid ? (uint8_t *)valid_bytes->ptr : nullptr;
-#define NQE_TREE(NU, NC) launch(ctx, "expr_tree_compact", expr_tree_compact_kernel<NU, NC>, grid, dim3(256), 0, P, kp, pv, to, km.n, km.ntiles, ow, ob, ov, ctx->d_flags)
+        const bool trig = program_has_trig(P);
+#define NQE_TREE(NU, NC)                                                                                                                                        \
+    do {                                                                                                                                                        \
+        if (trig) launch(ctx, "expr_tree_compact", expr_tree_compact_kernel<NU, NC, true>, grid, dim3(256), 0, P, kp, pv, to, km.n, km.ntiles, ow, ob, ov, ctx->d_flags); \
+        else launch(ctx, "expr_tree_compact", expr_tree_compact_kernel<NU, NC, false>, grid, dim3(256), 0, P, kp, pv, to, km.n, km.ntiles, ow, ob, ov, ctx->d_flags);    \
+    } while (0)
         if (needs_valid) { if (P.ncols <= 2) NQE_TREE(true, 2); else NQE_TREE(true, 4); }
         else { if (P.ncols <= 2) NQE_TREE(false, 2); else NQE_TREE(false, 4); }
 #undef NQE_TREE
@@ -1079,7 +1187,7 @@ bool project_specialised(nqe_ctx *ctx, const nqe_table *in, const nqe_expr_node 
             if (o.col < 0) return false;
             o.needs_valid = c.validity != nullptr || km.pvalid != nullptr;
             J.nulls = J.nulls || c.validity != nullptr;
-        } else if (rt.kind == NQE_EXPR_BINARY) {
+        } else if (is_op_node(rt.kind)) {
             bool nv = false;
             if (!build_program(in, t, root, &o.P, &nv)) return false;
             for (int i = 0; i < o.P.n; ++i) {
@@ -1191,7 +1299,7 @@ bool select_project_fused(nqe_ctx *ctx, const nqe_table *in, const nqe_expr_node
             o.col = slot_of(c.values->ptr, nullptr, c.dtype);
             if (o.col < 0) return false;
             S.proj_cols |= 1u << o.col;
-        } else if (rt.kind == NQE_EXPR_BINARY) {
+        } else if (is_op_node(rt.kind)) {
             bool nv = false;
             if (rt.out_dtype == NQE_BOOLEAN || !build_program(in, t, root, &o.P, &nv) || nv) return false;
             if (!renumber(o.P, &S.proj_cols)) return false;
@@ -1300,6 +1408,9 @@ bool aggregate_tree_specialised(nqe_ctx *ctx, const nqe_table *in, const nqe_exp
         std::vector<Node> t = parse(in, pred, pred_nodes, &root);
         bool nv = false;
         if (t[size_t(root)].kind != NQE_EXPR_BINARY || t[size_t(root)].out_dtype != NQE_BOOLEAN || !build_program(in, t, root, &G.pred, &nv) || nv) return false;
+        // a sin / cos step: under this kernel's 128-register cap (1024-thread workgroups) the library's argument reduction spills (70 VGPRs,
+        // 188 bytes of scratch offline), and nobody has measured that against the bitmap + static kernel path — which such predicates keep
+        if (program_has_trig(G.pred)) return false;
         if (!renumber(G.pred)) return false;
     }
     JitEntry *kernel = jit_aggregate_entry(ctx, G);

@@ -13,8 +13,12 @@
 // a hash of everything baked into the source (steps, dtypes, which columns carry validity, output form, baked divisors); other
 // literals and all pointers are kernel arguments, so `v * 2 > K` does not compile once per K.  Any failure — no libhiprtc, a
 // compile error — marks the entry failed and the interpreter stays: results never depend on the specialisation.
-// Semantics are those of apply_binary / ex_combine (device_utils.hpp, expr.hip), restated in the generated source; the parity
-// tests run every tree through both forms.
+// Semantics are those of apply_binary / apply_unary / ex_combine (device_utils.hpp, expr.hip), restated in the generated source.
+// The two forms are not compiled with the same contraction option (the library: hipcc's default; the generated source:
+// -ffp-contract=off and the pragma) and still agree bit for bit: the interpreter executes every step in its own iteration of a
+// run-time loop, so no multiply ever sits next to the add that could absorb it, and a unary step calls the same sin / cos of the
+// device library in both — precompiled bitcode whose own instructions are not re-contracted — with no fast-math option on either
+// side.  The parity tests run every tree through both forms.
 #pragma once
 
 #include <dlfcn.h>
@@ -154,6 +158,25 @@ std::pair<std::string, std::string> emit_steps(std::ostringstream &s, const ExPr
                 v = src == EX_LIT ? lit_valid : "false";
             }
         };
+        if (in.op >= EX_OP_UNARY) {
+            // the one-operand form: the value is mapped by the SAME device functions the interpreter calls (apply_unary, device_utils.hpp:
+            // abs = sign bit cleared, the device library's sin / cos, Tan = cos — quirk Q16), the validity passes through
+            // (aggregate_tree_specialised declines sin / cos predicates: gen_source_agg only ever sees abs)
+            if (a_st) { a = st.back() + "[r]"; av = stv.back(); st.pop_back(); stv.pop_back(); }
+            else operand(in.a_src, 0, a, av);
+            const std::string t = prefix + std::to_string(i), tv = t + "v";
+            const int f = in.op - EX_OP_UNARY;
+            s << "    u64 " << t << "[R];";
+            if (nulls) s << " bool " << tv << "[R];";
+            s << "\n#pragma unroll\n    for (int r = 0; r < R; ++r) {\n      const u64 a = " << a << ";\n";
+            if (nulls) s << "      " << tv << "[r] = " << av << ";\n";
+            if (f == NQE_UNARY_ABS) s << "      " << t << "[r] = a & 0x7fffffffffffffffull;\n";
+            else s << "      " << t << "[r] = d2u(" << (f == NQE_UNARY_SIN ? "sin" : "cos") << "(u2d(a)));\n";
+            s << "    }\n";
+            st.push_back(t);
+            stv.push_back(nulls ? tv + "[r]" : "in[r]");
+            continue;
+        }
         if (a_st && b_st) {
             b = st.back() + "[r]"; bv = stv.back(); st.pop_back(); stv.pop_back();
             a = st.back() + "[r]"; av = stv.back(); st.pop_back(); stv.pop_back();

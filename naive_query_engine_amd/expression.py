@@ -1,6 +1,6 @@
 """Host mirror of the reference's physical expressions.
 
-Same names and constructor arguments as src/physical_plan/expression/{column,literal,binary}.rs so
+Same names and constructor arguments as src/physical_plan/expression/{column,literal,binary,unary}.rs so
 plans are written exactly as in the reference's tests (e.g. selection.rs:145-155):
 
     add_expr = PhysicalBinaryExpr.create(ColumnExpr.try_create("id", None), Operator.Plus,
@@ -14,8 +14,8 @@ from __future__ import annotations
 
 from typing import List, Optional, Sequence
 
-from .arrow_host import (ErrorCode, Field, NqeExprNode, Operator, ScalarValue, Status, node_binary, node_column,
-                         node_literal)
+from .arrow_host import (ErrorCode, Field, NqeExprNode, Operator, ScalarValue, Status, UnaryOperator, node_binary, node_column,
+                         node_literal, node_unary)
 
 
 class PhysicalExpr:
@@ -94,6 +94,24 @@ class PhysicalBinaryExpr(PhysicalExpr):
         return f"({self.left!r} {self.op.name} {self.right!r})"
 
 
+class PhysicalUnaryExpr(PhysicalExpr):
+    """src/physical_plan/expression/unary.rs:46-109.  `name` and `return_type` are stored and, as in the reference's evaluate,
+    ignored (the planner passes "todo" and Int32, planner/mod.rs:208-217): the result is Float64 whatever they say."""
+
+    def __init__(self, expr: PhysicalExpr, func: UnaryOperator, name: str = "", return_type=None):
+        self.expr, self.func, self.name, self.return_type = expr, UnaryOperator(func), name, return_type
+
+    @staticmethod
+    def create(expr: PhysicalExpr, func: UnaryOperator, name: str = "", return_type=None) -> "PhysicalUnaryExpr":
+        return PhysicalUnaryExpr(expr, func, name, return_type)
+
+    def flatten(self, fields):
+        return self.expr.flatten(fields) + [node_unary(self.func)]
+
+    def __repr__(self):
+        return f"{self.func.name}({self.expr!r})"
+
+
 # small conveniences for tests / bench (not part of the reference surface)
 def col(i_or_name) -> ColumnExpr:
     return ColumnExpr.try_create(None, i_or_name) if isinstance(i_or_name, int) else ColumnExpr.try_create(i_or_name, None)
@@ -121,3 +139,7 @@ def lit_utf8(v) -> PhysicalLiteralExpr:
 
 def binop(l, op, r) -> PhysicalBinaryExpr:
     return PhysicalBinaryExpr.create(l, op, r)
+
+
+def unop(func, e) -> PhysicalUnaryExpr:
+    return PhysicalUnaryExpr.create(e, func, UnaryOperator(func).name.lower(), None)

@@ -46,6 +46,8 @@ struct ErrorCode : std::exception {
 // ---------------------------------------------------------------- logical_plan/expression.rs
 enum class Operator { Eq, NotEq, Lt, LtEq, Gt, GtEq, Plus, Minus, Multiply, Divide, Modulos, And, Or }; // :335-362
 enum class AggregateFunc { Count, Sum, Min, Max, Avg };                                                // :491-502
+// :392-422, same order = nqe_unary_operator; only the four math functions have a body (unary.rs:92-107), Tan is the cosine (quirk Q16)
+enum class UnaryOperator { Abs, Sin, Cos, Tan, Trim, LTrim, RTrim, CharacterLength, Lower, Upper, Repeat, Replace, Reverse, Substr };
 enum class DataType { Null = NQE_NULLTYPE, Boolean = NQE_BOOLEAN, Int64 = NQE_INT64, UInt64 = NQE_UINT64, Float64 = NQE_FLOAT64, Utf8 = NQE_UTF8 };
 enum class JoinType { Inner, Left, Right, Cross }; // logical_plan/plan.rs:134-139
 
@@ -266,6 +268,25 @@ struct PhysicalBinaryExpr : PhysicalExpr { // binary.rs:91-156
         nqe_expr_node n{};
         n.kind = NQE_EXPR_BINARY;
         n.op = int32_t(op);
+        out.push_back(n);
+    }
+};
+
+struct PhysicalUnaryExpr : PhysicalExpr { // unary.rs:46-109
+    PhysicalExprRef expr;
+    UnaryOperator func;
+    std::string name;       // stored and, as in the reference's evaluate, ignored (the planner passes "todo" and Int32,
+    DataType return_type;   // planner/mod.rs:208-217): the result is Float64 whatever they say
+    static PhysicalExprRef create(PhysicalExprRef e, UnaryOperator func, std::string name, DataType return_type) {
+        auto u = std::make_shared<PhysicalUnaryExpr>();
+        u->expr = std::move(e); u->func = func; u->name = std::move(name); u->return_type = return_type;
+        return u;
+    }
+    void flatten(const NaiveSchema &schema, std::vector<nqe_expr_node> &out) const override {
+        expr->flatten(schema, out);
+        nqe_expr_node n{};
+        n.kind = NQE_EXPR_UNARY;
+        n.op = int32_t(func);
         out.push_back(n);
     }
 };
