@@ -566,6 +566,26 @@ nqe_status nqe_join_table_release(nqe_join_table *jt);
  * NQE_ERR_OUT_OF_MEMORY. */
 nqe_status nqe_cross_join_execute(nqe_ctx *ctx, const nqe_table *left, const nqe_table *right, nqe_table **out);
 
+/* ------------------------------------------------------------------ nested loop join
+ * NestedLoopJoin::execute (nested_loop_join.rs:110-175) for one outer (left) batch and one inner
+ * (right) batch; the caller loops over the batch pairs outer-major, one output batch per pair (empty
+ * ones included), and nothing is kept between calls.  Quirk Q17: the row pair (x, y) is emitted iff
+ * both keys are valid and equal — Int64 / UInt64 by the 64-bit word, Float64 by IEEE == (NaN matches
+ * nothing, -0.0 matches 0.0), Utf8 by the bytes; a NULL key matches nothing (unlike the hash join,
+ * Q11).  Output rows are sorted by (x, y) ascending: the order of the reference's two loops.  The
+ * output holds all left columns taken by x, then all right columns taken by y (`take`: validity is
+ * preserved; Boolean and Utf8 payload columns are fine).  An empty side or no match gives a 0-row
+ * table with every column.
+ * Errors: a key index out of range NQE_ERR_NOT_SUPPORTED; key dtypes that differ NQE_ERR_PLAN; then
+ * any equal pair other than Int64 / UInt64 / Float64 / Utf8 NQE_ERR_NOT_SUPPORTED (the reference
+ * panics: unimplemented!()) — all three also at 0 rows, before any launch.  After the count pass and
+ * before the output is allocated: the positions plus every column beyond int64 or larger than the
+ * device NQE_ERR_OUT_OF_MEMORY; a Utf8 output column of more than INT32_MAX bytes
+ * NQE_ERR_NOT_SUPPORTED (arrow's take would overflow its int32 offsets).  Counts and positions are
+ * 64-bit: more than 2^32 output rows are legal. */
+nqe_status nqe_nested_loop_join_execute(nqe_ctx *ctx, const nqe_table *left, const nqe_table *right,
+                                        int32_t left_key, int32_t right_key, nqe_table **out);
+
 /* ------------------------------------------------------------------ take
  * arrow::compute::take(array, &Int64Array indices, None) over every column
  * (hash_join.rs:239,245): out[j] = in[indices[j]]; `indices` = Int64 column `idx_column` of

@@ -21,7 +21,8 @@
 //!   3. `src/datasource/mod.rs:17`:      one more method on `trait TableSource`:
 //!          `fn scan_device(&self, _projection: Option<Vec<usize>>) -> Option<Result<Vec<crate::physical_plan::GpuBatch>>> { None }`
 //!   4. `pub(crate)` on the fields of `ScanPlan` (scan.rs:19-22), `SelectionPlan` (selection.rs:23-27), `ProjectionPlan`
-//!      (projection.rs:18-23), `HashJoin::{left,right,on,schema}` (hash_join.rs:44-56), `CrossJoin::{left,right,schema}` (cross_join.rs:26-32), `PhysicalLimitPlan` (limit.rs:15-19),
+//!      (projection.rs:18-23), `HashJoin::{left,right,on,schema}` (hash_join.rs:44-56), `CrossJoin::{left,right,schema}` (cross_join.rs:26-32),
+//!      `NestedLoopJoin::{left,right,on,schema}` (nested_loop_join.rs:31-38), `PhysicalLimitPlan` (limit.rs:15-19),
 //!      `PhysicalOffsetPlan` (offset.rs:15-19), `PhysicalBinaryExpr` (expression/binary.rs:91-96) and `PhysicalUnaryExpr::{expr,func}`
 //!      (expression/unary.rs:46-51).
 //!   5. `src/physical_plan/aggregate/mod.rs:225`: one more method on `trait AggregateOperator`, one line in each of
@@ -51,7 +52,7 @@ use crate::error::{ErrorCode, Result};
 use crate::logical_plan::expression::{AggregateFunc, Column, ScalarValue};
 use crate::logical_plan::schema::NaiveSchema;
 use crate::physical_plan::{
-    ColumnExpr, CrossJoin, HashJoin, PhysicalAggregatePlan, PhysicalBinaryExpr, PhysicalExprRef, PhysicalLimitPlan, PhysicalLiteralExpr, PhysicalOffsetPlan,
+    ColumnExpr, CrossJoin, HashJoin, NestedLoopJoin, PhysicalAggregatePlan, PhysicalBinaryExpr, PhysicalExprRef, PhysicalLimitPlan, PhysicalLiteralExpr, PhysicalOffsetPlan,
     PhysicalPlan, PhysicalPlanRef, PhysicalUnaryExpr, ProjectionPlan, ScanPlan, SelectionPlan,
 };
 
@@ -103,6 +104,7 @@ extern "C" {
     fn nqe_hash_join_probe(ctx: *mut NqeCtx, build: *const NqeJoinTable, right: *const NqeTable, right_key: i32, out: *mut *mut NqeTable) -> i32;
     fn nqe_join_table_release(jt: *mut NqeJoinTable) -> i32;
     fn nqe_cross_join_execute(ctx: *mut NqeCtx, left: *const NqeTable, right: *const NqeTable, out: *mut *mut NqeTable) -> i32;
+    fn nqe_nested_loop_join_execute(ctx: *mut NqeCtx, left: *const NqeTable, right: *const NqeTable, left_key: i32, right_key: i32, out: *mut *mut NqeTable) -> i32;
 }
 
 // ------------------------------------------------------------------ context, device tables, upload, download
@@ -603,6 +605,43 @@ impl PhysicalPlan for GpuCrossJoin {
     fn as_gpu(&self) -> Option<&dyn GpuExec> { Some(self) }
 }
 
+/// NestedLoopJoin (nested_loop_join.rs:30-184): inner equi-join on on[0], one output batch per (outer, inner) batch pair, outer-major;
+/// quirk Q17: NULL keys match nothing, Float64 keys are joined with IEEE ==, rows by ascending (left row, right row), payload validity
+/// preserved; `join_type` is not read and nothing is kept between executions
+#[derive(Debug)]
+pub struct GpuNestedLoopJoin { left: PhysicalPlanRef, right: PhysicalPlanRef, on: Vec<(Column, Column)>, schema: NaiveSchema, ctx: Arc<GpuCtx> }
+impl GpuNestedLoopJoin {
+    pub fn create(ctx: Arc<GpuCtx>, left: PhysicalPlanRef, right: PhysicalPlanRef, on: Vec<(Column, Column)>, schema: NaiveSchema) -> PhysicalPlanRef {
+        Arc::new(Self { left, right, on, schema, ctx })
+    }
+}
+impl GpuExec for GpuNestedLoopJoin {
+    fn execute_device(&self) -> Result<Vec<GpuBatch>> {
+        let outer = child_device(&self.ctx, &self.left)?;
+        let inner = child_device(&self.ctx, &self.right)?;
+        // after the children, so a child's error wins (nested_loop_join.rs:99-103); on[0] only (:105)
+        let (lc, rc) = self.on.first().ok_or_else(|| ErrorCode::PlanError("Inner Join on Conditions can't not be empty".to_string()))?;
+        let mut out = vec![];
+        for o in &outer {
+            let lk = self.left.schema().index_of(&lc.name)? as i32; // by NAME, first match, in the outer loop (:111)
+            for i in &inner {
+                let rk = self.right.schema().index_of(&rc.name)? as i32;
+                let mut t = std::ptr::null_mut();
+                self.ctx.check(unsafe { nqe_nested_loop_join_execute(self.ctx.0, o.table.0, i.table.0, lk, rk, &mut t) })?;
+                out.push(GpuBatch::wrap(t));
+            }
+        }
+        Ok(out)
+    }
+}
+impl PhysicalPlan for GpuNestedLoopJoin {
+    fn schema(&self) -> &NaiveSchema { &self.schema }
+    fn children(&self) -> Result<Vec<PhysicalPlanRef>> { Ok(vec![self.left.clone(), self.right.clone()]) }
+    fn execute(&self) -> Result<Vec<RecordBatch>> { self.ctx.download_all(&self.execute_device()?, &self.schema) }
+    fn as_any(&self) -> &dyn Any { self }
+    fn as_gpu(&self) -> Option<&dyn GpuExec> { Some(self) }
+}
+
 /// PhysicalLimitPlan / PhysicalOffsetPlan (limit.rs:32-49, offset.rs:30-51) over device batches: whole batches are passed on,
 /// a cut batch is nqe_table_slice — so a LIMIT above a device operator downloads `n` rows, not the operator's whole result
 #[derive(Debug)]
@@ -666,8 +705,9 @@ impl GpuCtx {
 // ------------------------------------------------------------------ the rewrite pass (what rewrite.py / naive_db.hpp `rewrite` do)
 // The planner keeps building the plain tree (planner/mod.rs:42-182); this pass (db.rs:34-36, between create_physical_plan and
 // execute: patch item 6) substitutes the device operators bottom-up, fusing Projection∘Selection and Aggregate∘Selection.
-// A CrossJoin becomes GpuCrossJoin on one device; on a rank of a sharded deployment (`comm`) it is left as it is, like an operator
-// the pass does not know (NestedLoopJoin): children included, its `execute()` pulls host batches from whatever is below.
+// A CrossJoin becomes GpuCrossJoin and a NestedLoopJoin becomes GpuNestedLoopJoin on one device; on a rank of a sharded deployment
+// (`comm`) they are left as they are, like an operator the pass does not know: children included, its `execute()` pulls host batches
+// from whatever is below.
 pub fn rewrite(ctx: &Arc<GpuCtx>, plan: PhysicalPlanRef) -> Result<PhysicalPlanRef> { rewrite_sharded(ctx, None, plan) }
 /// the same pass for one rank of a multi-GPU deployment (`comm`: aggregates merge over the ranks, joins return this rank's rows)
 pub fn rewrite_sharded(ctx: &Arc<GpuCtx>, comm: Option<&Arc<GpuComm>>, plan: PhysicalPlanRef) -> Result<PhysicalPlanRef> {
@@ -702,6 +742,11 @@ pub fn rewrite_sharded(ctx: &Arc<GpuCtx>, comm: Option<&Arc<GpuComm>>, plan: Phy
     if let Some(c) = any.downcast_ref::<CrossJoin>() {
         if comm.is_none() {
             return Ok(GpuCrossJoin::create(ctx.clone(), rewrite(ctx, c.left.clone())?, rewrite(ctx, c.right.clone())?, c.schema.clone()));
+        }
+    }
+    if let Some(n) = any.downcast_ref::<NestedLoopJoin>() {
+        if comm.is_none() {
+            return Ok(GpuNestedLoopJoin::create(ctx.clone(), rewrite(ctx, n.left.clone())?, rewrite(ctx, n.right.clone())?, n.on.clone(), n.schema.clone()));
         }
     }
     if let Some(l) = any.downcast_ref::<PhysicalLimitPlan>() {

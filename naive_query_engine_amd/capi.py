@@ -28,7 +28,7 @@ SYMBOLS = [
     "nqe_table_unpack_words", "nqe_csv_infer_schema", "nqe_csv_read", "nqe_expr_evaluate",
     "nqe_filter", "nqe_selection_execute", "nqe_projection_execute", "nqe_selection_projection_execute",
     "nqe_aggregate_execute", "nqe_aggregate_partial", "nqe_aggregate_merge", "nqe_aggregate_merge_packed", "nqe_hash_join_execute",
-    "nqe_hash_join_build", "nqe_hash_join_probe", "nqe_join_table_release", "nqe_cross_join_execute", "nqe_take", "nqe_synth_fill",
+    "nqe_hash_join_build", "nqe_hash_join_probe", "nqe_join_table_release", "nqe_cross_join_execute", "nqe_nested_loop_join_execute", "nqe_take", "nqe_synth_fill",
     "nqe_device_alloc", "nqe_device_free",
     "nqe_comm_get_unique_id", "nqe_comm_rccl_version", "nqe_comm_create", "nqe_comm_create_custom", "nqe_comm_create_p2p", "nqe_comm_destroy", "nqe_comm_rank",
     "nqe_comm_world", "nqe_table_all_gather", "nqe_sharded_aggregate_execute", "nqe_sharded_hash_join_probe",
@@ -131,6 +131,7 @@ def lib():
         "nqe_hash_join_probe": (i32, [vp, vp, vp, i32, pvp]),
         "nqe_join_table_release": (i32, [vp]),
         "nqe_cross_join_execute": (i32, [vp, vp, vp, pvp]),
+        "nqe_nested_loop_join_execute": (i32, [vp, vp, vp, i32, i32, pvp]),
         "nqe_take": (i32, [vp, vp, vp, i32, pvp]),
         "nqe_synth_fill": (i32, [vp, i32, u64, i64, i64, u64, i64, vp]),
         "nqe_device_alloc": (i32, [vp, C.c_size_t, pvp]),
@@ -388,6 +389,13 @@ class Context:
         """CrossJoin::execute for one batch pair (quirk Q15): left[j % L] beside right[j % R] for j < L*R, no validity"""
         h = C.c_void_p()
         self.check(lib().nqe_cross_join_execute(self.handle, left.handle, right.handle, C.byref(h)))
+        return Table(self, h, derived_from=(left, right))
+
+    def nested_loop_join(self, left: "Table", right: "Table", left_key: int, right_key: int) -> "Table":
+        """NestedLoopJoin::execute for one batch pair (quirk Q17): the (x, y) with valid, equal keys in ascending (x, y) order; every
+        left column taken by x, then every right column by y, validity preserved"""
+        h = C.c_void_p()
+        self.check(lib().nqe_nested_loop_join_execute(self.handle, left.handle, right.handle, left_key, right_key, C.byref(h)))
         return Table(self, h, derived_from=(left, right))
 
     def take(self, table: "Table", idx_table: "Table", idx_column: int = 0) -> "Table":

@@ -676,6 +676,47 @@ struct CrossJoin : PhysicalPlan {
     }
 };
 
+// ---------------------------------------------------------------- physical_plan/nested_loop_join.rs:30-184
+// Inner equi-join on on[0], one output batch per (outer, inner) batch pair, outer-major.  Quirk Q17: NULL keys match nothing, Float64
+// keys are joined with IEEE ==, rows come out by ascending (left row, right row), payload validity is preserved; nothing is kept
+// between execute() calls.
+struct NestedLoopJoin : PhysicalPlan {
+    PhysicalPlanRef left, right;
+    std::vector<std::pair<Column, Column>> on;
+    JoinType join_type = JoinType::Inner; // stored, never read (:35-36)
+    NaiveSchema schema_;
+    static PhysicalPlanRef create(PhysicalPlanRef left, PhysicalPlanRef right, std::vector<std::pair<Column, Column>> on, JoinType jt, NaiveSchema schema) {
+        auto p = std::make_shared<NestedLoopJoin>();
+        p->left = std::move(left); p->right = std::move(right); p->on = std::move(on); p->join_type = jt; p->schema_ = std::move(schema);
+        return p;
+    }
+    const NaiveSchema &schema() const override { return schema_; }
+    std::vector<PhysicalPlanRef> children() const override { return {left, right}; }
+    std::vector<RecordBatch> execute() override {
+        std::vector<RecordBatch> outer = left->execute();
+        std::vector<RecordBatch> inner = right->execute();
+        if (on.empty()) throw ErrorCode(ErrorCode::PlanError, "Inner Join on Conditions can't not be empty"); // after the children (:99-103)
+        auto lcol = ColumnExpr::try_create(on[0].first.name, std::nullopt), rcol = ColumnExpr::try_create(on[0].second.name, std::nullopt); // on[0] only (:105)
+        std::vector<RecordBatch> out;
+        for (auto &o : outer) {
+            size_t lkey = lcol->resolve(o.schema()); // by NAME, in the outer loop (:111)
+            for (auto &i : inner) {
+                size_t rkey = rcol->resolve(i.schema());
+                nqe_table *t = nullptr;
+                o.ctx()->check(nqe_nested_loop_join_execute(o.ctx()->raw(), o.raw(), i.raw(), int32_t(lkey), int32_t(rkey), &t));
+                NaiveSchema s = schema_;
+                if (int32_t(s.fields().size()) != nqe_table_num_columns(t)) {
+                    std::vector<NaiveField> f = o.schema().fields();
+                    for (auto &x : i.schema().fields()) f.push_back(x);
+                    s = NaiveSchema(f);
+                }
+                out.push_back(o.with_table(s, t));
+            }
+        }
+        return out;
+    }
+};
+
 // ---------------------------------------------------------------- physical_plan/visitor.rs:4-24
 struct PhysicalPlanVisitor { // trait PhysicalPlanVistor
     virtual ~PhysicalPlanVisitor() = default;
@@ -782,6 +823,7 @@ inline PhysicalPlanRef rewrite(const PhysicalPlanRef &plan) {
     if (auto o = std::dynamic_pointer_cast<PhysicalOffsetPlan>(plan)) return PhysicalOffsetPlan::create(rewrite(o->input), o->n);
     if (auto j = std::dynamic_pointer_cast<HashJoin>(plan)) return HashJoin::create(rewrite(j->left), rewrite(j->right), j->on, j->join_type, j->schema_);
     if (auto c = std::dynamic_pointer_cast<CrossJoin>(plan)) return CrossJoin::create(rewrite(c->left), rewrite(c->right), c->join_type, c->schema_);
+    if (auto n = std::dynamic_pointer_cast<NestedLoopJoin>(plan)) return NestedLoopJoin::create(rewrite(n->left), rewrite(n->right), n->on, n->join_type, n->schema_);
     return plan; // scans, fused operators, operators this pass does not know
 }
 

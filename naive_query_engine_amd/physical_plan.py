@@ -493,3 +493,40 @@ class CrossJoin(PhysicalPlan):
                 fields = self._schema if len(self._schema) == t.num_columns else list(o.fields) + list(i.fields)
                 out.append(DeviceRecordBatch(fields, t))
         return out
+
+
+# ----------------------------------------------------------------------------- nested loop join
+class NestedLoopJoin(PhysicalPlan):
+    """src/physical_plan/nested_loop_join.rs:30-184 — inner equi-join on `on[0]`, one output batch per (outer, inner) batch pair,
+    outer-major (quirk Q17): NULL keys match nothing, Float64 keys are joined with IEEE ==, rows come out by ascending (left row,
+    right row), payload validity is preserved.  `join_type` is stored and never read; nothing is kept between execute() calls."""
+
+    def __init__(self, left, right, on, join_type, schema):
+        self.left, self.right, self.on, self.join_type, self._schema = left, right, list(on), join_type, list(schema)
+
+    @staticmethod
+    def create(left: PhysicalPlan, right: PhysicalPlan, on: Sequence[Tuple[ColumnRef, ColumnRef]], join_type, schema: NaiveSchema) -> "NestedLoopJoin":
+        return NestedLoopJoin(left, right, on, join_type, schema)
+
+    def schema(self):
+        return self._schema
+
+    def children(self):
+        return [self.left, self.right]
+
+    def execute(self):
+        outer = self.left.execute()
+        inner = self.right.execute()
+        if not self.on:  # after the children (:99-103): a child's error wins
+            raise ErrorCode(Status.PlanError, "Inner Join on Conditions can't not be empty")
+        lcol = ColumnExpr.try_create(self.on[0][0].name, None)  # only on[0] (:105), by NAME, first match
+        rcol = ColumnExpr.try_create(self.on[0][1].name, None)
+        out = []
+        for o in outer:
+            lkey = lcol.resolve(o.fields)  # in the outer loop (:111): a missing left column raises without inner batches
+            for i in inner:
+                rkey = rcol.resolve(i.fields)
+                t = o.table.ctx.nested_loop_join(o.table, i.table, lkey, rkey)
+                fields = self._schema if len(self._schema) == t.num_columns else list(o.fields) + list(i.fields)
+                out.append(DeviceRecordBatch(fields, t))
+        return out

@@ -19,7 +19,7 @@ from __future__ import annotations
 from typing import Dict, List, Optional, Sequence
 
 from .arrow_host import ErrorCode, Field, RecordBatch, Status
-from .physical_plan import (CrossJoin, CsvConfig, CsvTable, DeviceRecordBatch, HashJoin, MemTable, NaiveSchema, PhysicalAggregatePlan, PhysicalLimitPlan,
+from .physical_plan import (CrossJoin, CsvConfig, CsvTable, DeviceRecordBatch, HashJoin, MemTable, NaiveSchema, NestedLoopJoin, PhysicalAggregatePlan, PhysicalLimitPlan,
                             PhysicalOffsetPlan, PhysicalPlan, ProjectionPlan, ScanPlan, SelectionPlan, _ctx_of, _Materialized)
 
 
@@ -113,6 +113,8 @@ def rewrite(plan: PhysicalPlan) -> PhysicalPlan:
         return HashJoin.create(rewrite(plan.left), rewrite(plan.right), plan.on, plan.join_type, plan._schema)
     if isinstance(plan, CrossJoin):
         return CrossJoin.create(rewrite(plan.left), rewrite(plan.right), plan.join_type, plan._schema)
+    if isinstance(plan, NestedLoopJoin):
+        return NestedLoopJoin.create(rewrite(plan.left), rewrite(plan.right), plan.on, plan.join_type, plan._schema)
     return plan  # an operator this pass does not know: left alone, children included
 
 
