@@ -586,6 +586,30 @@ nqe_status nqe_cross_join_execute(nqe_ctx *ctx, const nqe_table *left, const nqe
 nqe_status nqe_nested_loop_join_execute(nqe_ctx *ctx, const nqe_table *left, const nqe_table *right,
                                         int32_t left_key, int32_t right_key, nqe_table **out);
 
+/* ------------------------------------------------------------------ order by
+ * ORDER BY over ONE table (the caller concatenates its batches first, as HashJoin::build does with
+ * concat_batches): the reference parses the clause and drops it (sql/planner.rs:159-162), so the
+ * definition — quirk Q18 — is arrow-rs' lexsort_to_indices followed by take.  Keys are
+ * lexicographic, keys[0] most significant; the sort is stable (rows that tie on every key keep
+ * their input order).  Int64 sorts signed, UInt64 unsigned, Boolean false < true, Float64 in the
+ * order min / max use (-0.0 ties with +0.0, every NaN ties with every NaN and is greater than +inf),
+ * Utf8 in byte order (memcmp, the shorter string first on a common prefix).  `descending` reverses
+ * the values of that key; its NULLs go first or last as `nulls_first` says, whatever `descending`
+ * says, and tie among themselves.  arrow-rs' SortOptions::default() is {descending 0, nulls_first
+ * 1}.  The output holds every column of `in` (validity preserved; Boolean and Utf8 payload columns
+ * are fine), taken by the first min(fetch, rows) positions of the order; fetch < 0: all rows,
+ * fetch = 0: a 0-row table with every column.
+ * Errors, all before any launch or allocation: num_keys <= 0 NQE_ERR_PLAN; a key column index out
+ * of range NQE_ERR_NOT_SUPPORTED; 2^32 rows or more NQE_ERR_NOT_SUPPORTED (the sort's payload is a
+ * 32-bit position). */
+typedef struct nqe_sort_key {
+    int32_t column;
+    int32_t descending;
+    int32_t nulls_first;
+} nqe_sort_key;
+nqe_status nqe_sort_execute(nqe_ctx *ctx, const nqe_table *in, const nqe_sort_key *keys, int32_t num_keys,
+                            int64_t fetch /* < 0: all rows */, nqe_table **out);
+
 /* ------------------------------------------------------------------ take
  * arrow::compute::take(array, &Int64Array indices, None) over every column
  * (hash_join.rs:239,245): out[j] = in[indices[j]]; `indices` = Int64 column `idx_column` of

@@ -68,6 +68,9 @@ pub union NqeValue { pub i64_: i64, pub u64_: u64, pub f64_: f64, pub boolean: i
 pub struct NqeExprNode { pub kind: i32, pub op: i32, pub column: i32, pub dtype: i32, pub is_null: i32, pub utf8_length: i32, pub value: NqeValue }
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct NqeAggregate { pub func: i32, pub column: i32 }
+/// nqe_sort_key: one ORDER BY key (arrow's SortOptions::default() is descending 0, nulls_first 1)
+#[repr(C)] #[derive(Clone, Copy, Debug)]
+pub struct NqeSortKey { pub column: i32, pub descending: i32, pub nulls_first: i32 }
 pub enum NqeCtx {}
 pub enum NqeTable {}
 pub enum NqeJoinTable {}
@@ -105,6 +108,7 @@ extern "C" {
     fn nqe_join_table_release(jt: *mut NqeJoinTable) -> i32;
     fn nqe_cross_join_execute(ctx: *mut NqeCtx, left: *const NqeTable, right: *const NqeTable, out: *mut *mut NqeTable) -> i32;
     fn nqe_nested_loop_join_execute(ctx: *mut NqeCtx, left: *const NqeTable, right: *const NqeTable, left_key: i32, right_key: i32, out: *mut *mut NqeTable) -> i32;
+    fn nqe_sort_execute(ctx: *mut NqeCtx, input: *const NqeTable, keys: *const NqeSortKey, num_keys: i32, fetch: i64, out: *mut *mut NqeTable) -> i32;
 }
 
 // ------------------------------------------------------------------ context, device tables, upload, download
@@ -642,6 +646,36 @@ impl PhysicalPlan for GpuNestedLoopJoin {
     fn as_gpu(&self) -> Option<&dyn GpuExec> { Some(self) }
 }
 
+/// ORDER BY (quirk Q18: the reference drops the clause, sql/planner.rs:159-162; the definition is lexsort_to_indices + take): the input
+/// batches are concatenated and ONE batch with the input's schema leaves, stably sorted by `keys` (column index, SortOptions), first key
+/// most significant, cut to `fetch` rows when given.  The reference's planner builds no such operator: a front end that plans ORDER BY
+/// creates it directly, and `rewrite` folds a PhysicalLimitPlan above it into `fetch`.
+#[derive(Debug)]
+pub struct GpuSortPlan { input: PhysicalPlanRef, keys: Vec<NqeSortKey>, fetch: Option<usize>, ctx: Arc<GpuCtx> }
+impl GpuSortPlan {
+    pub fn create(ctx: Arc<GpuCtx>, input: PhysicalPlanRef, keys: Vec<NqeSortKey>, fetch: Option<usize>) -> PhysicalPlanRef {
+        Arc::new(Self { input, keys, fetch, ctx })
+    }
+}
+impl GpuExec for GpuSortPlan {
+    fn execute_device(&self) -> Result<Vec<GpuBatch>> {
+        let batches = child_device(&self.ctx, &self.input)?;
+        if batches.is_empty() { return Err(ErrorCode::NotSupported("order by over an empty batch list is not supported on the device path".to_string())); }
+        let all = self.ctx.concat(&batches)?;
+        let fetch = match self.fetch { Some(n) => n as i64, None => -1 };
+        let mut t = std::ptr::null_mut();
+        self.ctx.check(unsafe { nqe_sort_execute(self.ctx.0, all.table.0, self.keys.as_ptr(), self.keys.len() as i32, fetch, &mut t) })?;
+        Ok(vec![GpuBatch::wrap(t)])
+    }
+}
+impl PhysicalPlan for GpuSortPlan {
+    fn schema(&self) -> &NaiveSchema { self.input.schema() }
+    fn children(&self) -> Result<Vec<PhysicalPlanRef>> { Ok(vec![self.input.clone()]) }
+    fn execute(&self) -> Result<Vec<RecordBatch>> { self.ctx.download_all(&self.execute_device()?, self.schema()) }
+    fn as_any(&self) -> &dyn Any { self }
+    fn as_gpu(&self) -> Option<&dyn GpuExec> { Some(self) }
+}
+
 /// PhysicalLimitPlan / PhysicalOffsetPlan (limit.rs:32-49, offset.rs:30-51) over device batches: whole batches are passed on,
 /// a cut batch is nqe_table_slice — so a LIMIT above a device operator downloads `n` rows, not the operator's whole result
 #[derive(Debug)]
@@ -750,6 +784,10 @@ pub fn rewrite_sharded(ctx: &Arc<GpuCtx>, comm: Option<&Arc<GpuComm>>, plan: Phy
         }
     }
     if let Some(l) = any.downcast_ref::<PhysicalLimitPlan>() {
+        if let Some(s) = l.input.as_any().downcast_ref::<GpuSortPlan>() { // the sort takes only the first n rows (an offset over a sort stays)
+            let fetch = match s.fetch { Some(f) => f.min(l.n), None => l.n };
+            return Ok(GpuSortPlan::create(ctx.clone(), rewrite(ctx, s.input.clone())?, s.keys.clone(), Some(fetch)));
+        }
         return Ok(GpuLimitPlan::create_limit(ctx.clone(), rewrite(ctx, l.input.clone())?, l.n));
     }
     if let Some(o) = any.downcast_ref::<PhysicalOffsetPlan>() {

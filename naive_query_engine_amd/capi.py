@@ -28,7 +28,7 @@ SYMBOLS = [
     "nqe_table_unpack_words", "nqe_csv_infer_schema", "nqe_csv_read", "nqe_expr_evaluate",
     "nqe_filter", "nqe_selection_execute", "nqe_projection_execute", "nqe_selection_projection_execute",
     "nqe_aggregate_execute", "nqe_aggregate_partial", "nqe_aggregate_merge", "nqe_aggregate_merge_packed", "nqe_hash_join_execute",
-    "nqe_hash_join_build", "nqe_hash_join_probe", "nqe_join_table_release", "nqe_cross_join_execute", "nqe_nested_loop_join_execute", "nqe_take", "nqe_synth_fill",
+    "nqe_hash_join_build", "nqe_hash_join_probe", "nqe_join_table_release", "nqe_cross_join_execute", "nqe_nested_loop_join_execute", "nqe_sort_execute", "nqe_take", "nqe_synth_fill",
     "nqe_device_alloc", "nqe_device_free",
     "nqe_comm_get_unique_id", "nqe_comm_rccl_version", "nqe_comm_create", "nqe_comm_create_custom", "nqe_comm_create_p2p", "nqe_comm_destroy", "nqe_comm_rank",
     "nqe_comm_world", "nqe_table_all_gather", "nqe_sharded_aggregate_execute", "nqe_sharded_hash_join_probe",
@@ -55,6 +55,11 @@ class ArrowArrayStruct(C.Structure):
     """struct ArrowArray of the Arrow C Data Interface (80 bytes)"""
     _fields_ = [("length", C.c_int64), ("null_count", C.c_int64), ("offset", C.c_int64), ("n_buffers", C.c_int64), ("n_children", C.c_int64),
                 ("buffers", C.c_void_p), ("children", C.c_void_p), ("dictionary", C.c_void_p), ("release", C.c_void_p), ("private_data", C.c_void_p)]
+
+
+class NqeSortKey(C.Structure):
+    """nqe_sort_key (include/nqe.h): one ORDER BY key; arrow-rs' SortOptions::default() is descending 0, nulls_first 1"""
+    _fields_ = [("column", C.c_int32), ("descending", C.c_int32), ("nulls_first", C.c_int32)]
 
 
 _P2P_SEND_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p)
@@ -132,6 +137,7 @@ def lib():
         "nqe_join_table_release": (i32, [vp]),
         "nqe_cross_join_execute": (i32, [vp, vp, vp, pvp]),
         "nqe_nested_loop_join_execute": (i32, [vp, vp, vp, i32, i32, pvp]),
+        "nqe_sort_execute": (i32, [vp, vp, C.POINTER(NqeSortKey), i32, i64, pvp]),
         "nqe_take": (i32, [vp, vp, vp, i32, pvp]),
         "nqe_synth_fill": (i32, [vp, i32, u64, i64, i64, u64, i64, vp]),
         "nqe_device_alloc": (i32, [vp, C.c_size_t, pvp]),
@@ -397,6 +403,24 @@ class Context:
         h = C.c_void_p()
         self.check(lib().nqe_nested_loop_join_execute(self.handle, left.handle, right.handle, left_key, right_key, C.byref(h)))
         return Table(self, h, derived_from=(left, right))
+
+    def order_by(self, table: "Table", keys, fetch: Optional[int] = None) -> "Table":
+        """ORDER BY over one table (quirk Q18: arrow-rs' lexsort_to_indices + take): a stable sort by `keys`, first key most
+        significant; a key is a column index or (column, descending=False, nulls_first=True).  `fetch`: only the first `fetch` rows"""
+        ks = [(k, False, True) if isinstance(k, int) else tuple(k) + (False, True)[len(k) - 1:] for k in keys]
+        arr = (NqeSortKey * max(1, len(ks)))(*[NqeSortKey(int(c), int(bool(d)), int(bool(nf))) for c, d, nf in ks])
+        h = C.c_void_p()
+        self.check(lib().nqe_sort_execute(self.handle, table.handle, arr, len(ks), -1 if fetch is None else int(fetch), C.byref(h)))
+        return Table(self, h)
+
+    def append_columns(self, table: "Table", extras: Sequence["Table"]) -> "Table":
+        """a zero-copy table of `table`'s columns followed by column 0 of every table of `extras` (the buffers are borrowed: the
+        result keeps its parents alive)"""
+        infos = [table.column_info(i) for i in range(table.num_columns)] + [e.column_info(0) for e in extras]
+        arr = (NqeColumn * max(1, len(infos)))(*infos)
+        h = C.c_void_p()
+        self.check(lib().nqe_table_create(self.handle, arr, len(infos), C.byref(h)))
+        return Table(self, h, derived_from=(table, *extras), view=True)
 
     def take(self, table: "Table", idx_table: "Table", idx_column: int = 0) -> "Table":
         h = C.c_void_p()

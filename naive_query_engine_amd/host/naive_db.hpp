@@ -16,6 +16,7 @@
 // libnqe_hip.so.  `Result<T>` of the reference is a thrown `ErrorCode` here.
 #pragma once
 
+#include <algorithm>
 #include <cstring>
 #include <fstream>
 #include <iterator>
@@ -717,6 +718,85 @@ struct NestedLoopJoin : PhysicalPlan {
     }
 };
 
+// ---------------------------------------------------------------- order by (no reference file: sql/planner.rs:159-162 drops the clause)
+// Quirk Q18: what arrow-rs' lexsort_to_indices + take give.  The input batches are concatenated and ONE batch with the input's schema
+// leaves: a stable sort by sort_exprs, first key most significant, cut to `fetch` rows when given.  A bare ColumnExpr key is passed by
+// index; any other expression is evaluated into a temporary column that the output drops again.
+struct PhysicalSortExpr {
+    PhysicalExprRef expr;
+    bool descending = false, nulls_first = true; // arrow-rs' SortOptions::default()
+    PhysicalSortExpr(PhysicalExprRef e, bool desc = false, bool nf = true) : expr(std::move(e)), descending(desc), nulls_first(nf) {}
+};
+struct PhysicalSortPlan : PhysicalPlan {
+    PhysicalPlanRef input;
+    std::vector<PhysicalSortExpr> sort_exprs;
+    std::optional<size_t> fetch;
+    static PhysicalPlanRef create(PhysicalPlanRef input, std::vector<PhysicalSortExpr> sort_exprs, std::optional<size_t> fetch = std::nullopt) {
+        auto p = std::make_shared<PhysicalSortPlan>();
+        p->input = std::move(input); p->sort_exprs = std::move(sort_exprs); p->fetch = fetch;
+        return p;
+    }
+    const NaiveSchema &schema() const override { return input->schema(); }
+    std::vector<PhysicalPlanRef> children() const override { return {input}; }
+    std::vector<RecordBatch> execute() override {
+        std::vector<RecordBatch> batches = input->execute();
+        if (batches.empty()) throw ErrorCode(ErrorCode::NotSupported, "order by over an empty batch list is not supported on the device path");
+        const ContextRef &ctx = batches[0].ctx();
+        const NaiveSchema &s = batches[0].schema();
+        auto release = [](nqe_table *p) { nqe_table_release(p); };
+        std::vector<std::shared_ptr<nqe_table>> guards;
+        nqe_table *in = batches[0].raw();
+        if (batches.size() > 1) {
+            std::vector<const nqe_table *> parts;
+            for (auto &b : batches) parts.push_back(b.raw());
+            nqe_table *c = nullptr;
+            ctx->check(nqe_table_concat(ctx->raw(), parts.data(), int32_t(parts.size()), &c));
+            guards.emplace_back(c, release);
+            in = c;
+        }
+        const int32_t ncols = nqe_table_num_columns(in);
+        std::vector<nqe_column> cols; // `in`'s columns and the temporaries, borrowed, once an expression key asks for them
+        std::vector<nqe_sort_key> keys;
+        for (auto &e : sort_exprs) {
+            int32_t col;
+            if (const ColumnExpr *c = e.expr->as_column()) {
+                col = int32_t(c->resolve(s));
+            } else {
+                std::vector<nqe_expr_node> nodes;
+                e.expr->flatten(s, nodes);
+                nqe_table *t = nullptr;
+                ctx->check(nqe_expr_evaluate(ctx->raw(), in, nodes.data(), int32_t(nodes.size()), &t));
+                guards.emplace_back(t, release);
+                if (cols.empty()) {
+                    cols.resize(size_t(ncols));
+                    for (int32_t i = 0; i < ncols; ++i) ctx->check(nqe_table_column(in, i, &cols[size_t(i)]));
+                }
+                nqe_column tc;
+                ctx->check(nqe_table_column(t, 0, &tc));
+                cols.push_back(tc);
+                col = int32_t(cols.size()) - 1;
+            }
+            keys.push_back(nqe_sort_key{col, e.descending ? 1 : 0, e.nulls_first ? 1 : 0});
+        }
+        const int64_t f = fetch ? int64_t(*fetch) : int64_t(-1);
+        nqe_table *out = nullptr;
+        if (cols.empty()) {
+            ctx->check(nqe_sort_execute(ctx->raw(), in, keys.data(), int32_t(keys.size()), f, &out));
+            return {batches[0].with_table(s, out)};
+        }
+        nqe_table *wide = nullptr;
+        ctx->check(nqe_table_create(ctx->raw(), cols.data(), int32_t(cols.size()), &wide));
+        guards.emplace_back(wide, release);
+        nqe_table *sorted = nullptr;
+        ctx->check(nqe_sort_execute(ctx->raw(), wide, keys.data(), int32_t(keys.size()), f, &sorted));
+        guards.emplace_back(sorted, release);
+        std::vector<int32_t> keep(static_cast<size_t>(ncols));
+        for (int32_t i = 0; i < ncols; ++i) keep[size_t(i)] = i;
+        ctx->check(nqe_table_project(ctx->raw(), sorted, keep.data(), ncols, &out));
+        return {batches[0].with_table(s, out)};
+    }
+};
+
 // ---------------------------------------------------------------- physical_plan/visitor.rs:4-24
 struct PhysicalPlanVisitor { // trait PhysicalPlanVistor
     virtual ~PhysicalPlanVisitor() = default;
@@ -819,7 +899,12 @@ inline PhysicalPlanRef rewrite(const PhysicalPlanRef &plan) {
         return out;
     }
     if (auto s = std::dynamic_pointer_cast<SelectionPlan>(plan)) return SelectionPlan::create(rewrite(s->input), s->expr);
-    if (auto l = std::dynamic_pointer_cast<PhysicalLimitPlan>(plan)) return PhysicalLimitPlan::create(rewrite(l->input), l->n);
+    if (auto l = std::dynamic_pointer_cast<PhysicalLimitPlan>(plan)) {
+        if (auto srt = std::dynamic_pointer_cast<PhysicalSortPlan>(l->input)) // the sort takes only the first n rows (an offset over a sort stays as it is)
+            return PhysicalSortPlan::create(rewrite(srt->input), srt->sort_exprs, srt->fetch ? std::min(*srt->fetch, l->n) : l->n);
+        return PhysicalLimitPlan::create(rewrite(l->input), l->n);
+    }
+    if (auto srt = std::dynamic_pointer_cast<PhysicalSortPlan>(plan)) return PhysicalSortPlan::create(rewrite(srt->input), srt->sort_exprs, srt->fetch);
     if (auto o = std::dynamic_pointer_cast<PhysicalOffsetPlan>(plan)) return PhysicalOffsetPlan::create(rewrite(o->input), o->n);
     if (auto j = std::dynamic_pointer_cast<HashJoin>(plan)) return HashJoin::create(rewrite(j->left), rewrite(j->right), j->on, j->join_type, j->schema_);
     if (auto c = std::dynamic_pointer_cast<CrossJoin>(plan)) return CrossJoin::create(rewrite(c->left), rewrite(c->right), c->join_type, c->schema_);

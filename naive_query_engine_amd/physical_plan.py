@@ -530,3 +530,58 @@ class NestedLoopJoin(PhysicalPlan):
                 fields = self._schema if len(self._schema) == t.num_columns else list(o.fields) + list(i.fields)
                 out.append(DeviceRecordBatch(fields, t))
         return out
+
+
+# ----------------------------------------------------------------------------- order by
+class PhysicalSortExpr:
+    """one ORDER BY key: an expression with arrow-rs' SortOptions (default: ascending, nulls first)"""
+
+    def __init__(self, expr: PhysicalExpr, descending: bool = False, nulls_first: bool = True):
+        self.expr, self.descending, self.nulls_first = expr, bool(descending), bool(nulls_first)
+
+    @staticmethod
+    def create(expr: PhysicalExpr, descending: bool = False, nulls_first: bool = True) -> "PhysicalSortExpr":
+        return PhysicalSortExpr(expr, descending, nulls_first)
+
+    def __repr__(self):
+        return f"PhysicalSortExpr({self.expr!r}, descending={self.descending}, nulls_first={self.nulls_first})"
+
+
+class PhysicalSortPlan(PhysicalPlan):
+    """ORDER BY (quirk Q18; the reference drops the clause, sql/planner.rs:159-162): what lexsort_to_indices + take give.  The input
+    batches are concatenated (global order needs one output, as HashJoin::build's concat_batches) and ONE batch with the input's
+    schema leaves: a stable sort by `sort_exprs`, first key most significant, cut to `fetch` rows when given.  A key that is a bare
+    ColumnExpr is passed by index; any other expression is evaluated into a temporary column that the output drops again."""
+
+    def __init__(self, input: PhysicalPlan, sort_exprs: Sequence[PhysicalSortExpr], fetch: Optional[int] = None):
+        self.input, self.sort_exprs, self.fetch = input, list(sort_exprs), fetch
+
+    @staticmethod
+    def create(input: PhysicalPlan, sort_exprs: Sequence[PhysicalSortExpr], fetch: Optional[int] = None) -> "PhysicalSortPlan":
+        return PhysicalSortPlan(input, sort_exprs, fetch)
+
+    def schema(self):
+        return self.input.schema()
+
+    def children(self):
+        return [self.input]
+
+    def execute(self):
+        batches = self.input.execute()
+        if not batches:
+            raise ErrorCode(Status.NotSupported, "order by over an empty batch list is not supported on the device path")
+        ctx = _ctx_of(batches)
+        fields = batches[0].fields
+        table = batches[0].table if len(batches) == 1 else ctx.concat([b.table for b in batches])
+        keys, temps = [], []
+        for e in self.sort_exprs:
+            if isinstance(e.expr, ColumnExpr):
+                col = e.expr.resolve(fields)
+            else:
+                temps.append(ctx.expr_evaluate(table, e.expr.flatten(fields)))
+                col = len(fields) + len(temps) - 1
+            keys.append((col, e.descending, e.nulls_first))
+        if not temps:
+            return [DeviceRecordBatch(fields, ctx.order_by(table, keys, self.fetch))]
+        out = ctx.order_by(ctx.append_columns(table, temps), keys, self.fetch)
+        return [DeviceRecordBatch(fields, ctx.project(out, list(range(len(fields)))))]

@@ -4,6 +4,7 @@ aggregate over a selection, …) and substitutes the subtrees the device execute
 
     ProjectionPlan(SelectionPlan(x))          →  FusedSelectionProjectionPlan(x)      nqe_selection_projection_execute
     PhysicalAggregatePlan(SelectionPlan(x))   →  FusedSelectionAggregatePlan(x)       nqe_aggregate_execute with its predicate argument
+    PhysicalLimitPlan(PhysicalSortPlan(x))    →  PhysicalSortPlan(x, fetch = n)       nqe_sort_execute with its fetch argument
 
 Everything else keeps its operator, with rewritten children.  The pass walks the tree through `children()` exactly as the
 reference's `_visit_physical_plan` does (src/physical_plan/visitor.rs:12-24: pre_visit, children in order, post_visit) —
@@ -20,7 +21,7 @@ from typing import Dict, List, Optional, Sequence
 
 from .arrow_host import ErrorCode, Field, RecordBatch, Status
 from .physical_plan import (CrossJoin, CsvConfig, CsvTable, DeviceRecordBatch, HashJoin, MemTable, NaiveSchema, NestedLoopJoin, PhysicalAggregatePlan, PhysicalLimitPlan,
-                            PhysicalOffsetPlan, PhysicalPlan, ProjectionPlan, ScanPlan, SelectionPlan, _ctx_of, _Materialized)
+                            PhysicalOffsetPlan, PhysicalPlan, PhysicalSortPlan, ProjectionPlan, ScanPlan, SelectionPlan, _ctx_of, _Materialized)
 
 
 # ----------------------------------------------------------------------------- visitor.rs:4-24
@@ -106,7 +107,12 @@ def rewrite(plan: PhysicalPlan) -> PhysicalPlan:
     if isinstance(plan, SelectionPlan):
         return SelectionPlan.create(rewrite(plan.input), plan.expr)
     if isinstance(plan, PhysicalLimitPlan):
+        if isinstance(plan.input, PhysicalSortPlan):  # the sort takes only the first n rows (an offset over a sort stays as it is)
+            srt = plan.input
+            return PhysicalSortPlan.create(rewrite(srt.input), srt.sort_exprs, plan.n if srt.fetch is None else min(plan.n, srt.fetch))
         return PhysicalLimitPlan.create(rewrite(plan.input), plan.n)
+    if isinstance(plan, PhysicalSortPlan):
+        return PhysicalSortPlan.create(rewrite(plan.input), plan.sort_exprs, plan.fetch)
     if isinstance(plan, PhysicalOffsetPlan):
         return PhysicalOffsetPlan.create(rewrite(plan.input), plan.n)
     if isinstance(plan, HashJoin):
