@@ -550,6 +550,40 @@ nqe_status nqe_hash_join_probe(nqe_ctx *ctx, const nqe_join_table *build, const 
                                int32_t right_key, nqe_table **out);
 nqe_status nqe_join_table_release(nqe_join_table *jt);
 
+/* ------------------------------------------------------------------ outer hash joins
+ * HashJoin honouring `join_type` — quirk Q19: the reference's planner builds JoinType::Left / Right plans
+ * (sql/planner.rs:221-225) and HashJoin stores the type without reading it (hash_join.rs:48-49).  The MATCH RELATION is exactly
+ * nqe_hash_join_probe's, Q11 included: left = build side, right = probe side, key validity ignored, the raw 8-byte slot (the
+ * bytes for Utf8) compared, the same key dtypes and errors.  So LEFT JOIN ⊇ JOIN holds against this library's own inner join
+ * (nqe_nested_loop_join_execute, Q17, keeps its different relation: there a NULL key matches nothing).
+ *   probe-preserving (RIGHT): nqe_hash_join_probe_outer with NQE_JOIN_KEEP_PROBE — one output batch per probe batch,
+ *     probe-row-major; a matched probe row emits its matches in ascending build row (the inner join's rows, in its order), a
+ *     probe row without a match emits ONE row in its place with every left column NULL.
+ *   build-preserving (LEFT): create marks for the join table, pass them to every nqe_hash_join_probe_outer call (the outputs
+ *     are the inner join's; the marks record which build rows matched), then nqe_hash_join_unmatched_build gives one final
+ *     batch — possibly of 0 rows — with every build row that matched in none of the probes, in ascending build row, followed by
+ *     num_right all-NULL columns of the given nqe_dtype (the probe side's schema).
+ *   FULL: both together.
+ * With flags = 0 and marks = NULL the output equals nqe_hash_join_probe's, column for column and bit for bit (the outer path
+ * is one general count / scan / write path over every build form and takes none of the inner join's fused tiers).
+ * NULL-extended cells hold 0 (word columns), a false bit (Boolean) or a zero-length string (Utf8); an output column has a
+ * validity buffer iff its source has one or the batch contains a NULL-extended row on that side; null_count is exact.
+ * Nothing is kept between calls except what the marks record.  Marks are bound to one join table and must be released before it.
+ * Errors, decided before any launch: key index / key dtypes / the 32-column limit as nqe_hash_join_probe;
+ * NQE_ERR_INVALID_ARGUMENT for unknown flag bits, marks created for another table or on another context, NULL marks in
+ * nqe_hash_join_unmatched_build, num_right < 0, a dtype outside nqe_dtype (NQE_NULLTYPE: NQE_ERR_NOT_SUPPORTED).  After the
+ * count pass: a 4096-row probe tile whose output exceeds 2^32 rows is NQE_ERR_OUT_OF_MEMORY, as in the inner join — nothing of
+ * the output's size is allocated and no output is written, but the count pass has run: marks passed to that call hold the
+ * matches of the refused batch. */
+typedef struct nqe_join_marks nqe_join_marks; /* which build rows have matched so far; bound to one join table */
+nqe_status nqe_join_marks_create(nqe_ctx *ctx, const nqe_join_table *build, nqe_join_marks **out);
+nqe_status nqe_join_marks_release(nqe_join_marks *marks);
+#define NQE_JOIN_KEEP_PROBE 1u
+nqe_status nqe_hash_join_probe_outer(nqe_ctx *ctx, const nqe_join_table *build, const nqe_table *right, int32_t right_key,
+                                     uint32_t flags, nqe_join_marks *marks /* may be NULL */, nqe_table **out);
+nqe_status nqe_hash_join_unmatched_build(nqe_ctx *ctx, const nqe_join_table *build, const nqe_join_marks *marks,
+                                         const int32_t *right_dtypes, int32_t num_right, nqe_table **out);
+
 /* ------------------------------------------------------------------ cross join
  * CrossJoin::execute (cross_join.rs:55-185) for one outer (left) batch and one inner (right)
  * batch; the caller loops over the batch pairs outer-major, one output batch per pair, and a side

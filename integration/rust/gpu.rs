@@ -50,6 +50,7 @@ use crate::catalog::Catalog;
 use crate::datasource::{TableRef, TableSource};
 use crate::error::{ErrorCode, Result};
 use crate::logical_plan::expression::{AggregateFunc, Column, ScalarValue};
+use crate::logical_plan::plan::JoinType;
 use crate::logical_plan::schema::NaiveSchema;
 use crate::physical_plan::{
     ColumnExpr, CrossJoin, HashJoin, NestedLoopJoin, PhysicalAggregatePlan, PhysicalBinaryExpr, PhysicalExprRef, PhysicalLimitPlan, PhysicalLiteralExpr, PhysicalOffsetPlan,
@@ -74,6 +75,8 @@ pub struct NqeSortKey { pub column: i32, pub descending: i32, pub nulls_first: i
 pub enum NqeCtx {}
 pub enum NqeTable {}
 pub enum NqeJoinTable {}
+pub enum NqeJoinMarks {}
+pub const NQE_JOIN_KEEP_PROBE: u32 = 1;
 pub enum NqeComm {}
 
 // nqe_expr_kind; nqe_unary_operator is `enum UnaryOperator` in declaration order (expression.rs:392-422): Abs = 0, Sin = 1, Cos = 2, Tan = 3,
@@ -106,6 +109,12 @@ extern "C" {
     fn nqe_hash_join_build(ctx: *mut NqeCtx, left: *const NqeTable, left_key: i32, out: *mut *mut NqeJoinTable) -> i32;
     fn nqe_hash_join_probe(ctx: *mut NqeCtx, build: *const NqeJoinTable, right: *const NqeTable, right_key: i32, out: *mut *mut NqeTable) -> i32;
     fn nqe_join_table_release(jt: *mut NqeJoinTable) -> i32;
+    fn nqe_join_marks_create(ctx: *mut NqeCtx, build: *const NqeJoinTable, out: *mut *mut NqeJoinMarks) -> i32;
+    fn nqe_join_marks_release(marks: *mut NqeJoinMarks) -> i32;
+    fn nqe_hash_join_probe_outer(ctx: *mut NqeCtx, build: *const NqeJoinTable, right: *const NqeTable, right_key: i32, flags: u32, marks: *mut NqeJoinMarks,
+                                 out: *mut *mut NqeTable) -> i32;
+    fn nqe_hash_join_unmatched_build(ctx: *mut NqeCtx, build: *const NqeJoinTable, marks: *const NqeJoinMarks, right_dtypes: *const i32, num_right: i32,
+                                     out: *mut *mut NqeTable) -> i32;
     fn nqe_cross_join_execute(ctx: *mut NqeCtx, left: *const NqeTable, right: *const NqeTable, out: *mut *mut NqeTable) -> i32;
     fn nqe_nested_loop_join_execute(ctx: *mut NqeCtx, left: *const NqeTable, right: *const NqeTable, left_key: i32, right_key: i32, out: *mut *mut NqeTable) -> i32;
     fn nqe_sort_execute(ctx: *mut NqeCtx, input: *const NqeTable, keys: *const NqeSortKey, num_keys: i32, fetch: i64, out: *mut *mut NqeTable) -> i32;
@@ -570,6 +579,76 @@ impl GpuExec for GpuHashJoin {
     }
 }
 impl PhysicalPlan for GpuHashJoin {
+    fn schema(&self) -> &NaiveSchema { &self.schema }
+    fn children(&self) -> Result<Vec<PhysicalPlanRef>> { Ok(vec![self.left.clone(), self.right.clone()]) }
+    fn execute(&self) -> Result<Vec<RecordBatch>> { self.ctx.download_all(&self.execute_device()?, &self.schema) }
+    fn as_any(&self) -> &dyn Any { self }
+    fn as_gpu(&self) -> Option<&dyn GpuExec> { Some(self) }
+}
+
+/// owned marks handle (nqe_join_marks): which build rows of one join table have matched so far; dropped before its join table
+struct GpuJoinMarks(*mut NqeJoinMarks);
+impl Drop for GpuJoinMarks { fn drop(&mut self) { unsafe { nqe_join_marks_release(self.0); } } }
+
+/// HashJoin honouring `join_type` (quirk Q19; hash_join.rs:48-49 stores the type and never reads it).  The match relation is
+/// GpuHashJoin's, Q11 included.  Inner: the inner join.  Right: a probe row without a match emits one row with every left column NULL.
+/// Left: the probe batches' outputs are the inner join's; one final batch — always emitted, possibly with 0 rows — holds the build rows
+/// that matched in no probe batch, in ascending build row, with every right column NULL.  Cross is a PlanError.
+#[derive(Debug)]
+pub struct GpuHashOuterJoin {
+    left: PhysicalPlanRef, right: PhysicalPlanRef, on: Vec<(Column, Column)>, join_type: JoinType, schema: NaiveSchema, ctx: Arc<GpuCtx>,
+}
+impl GpuHashOuterJoin {
+    pub fn create(ctx: Arc<GpuCtx>, left: PhysicalPlanRef, right: PhysicalPlanRef, on: Vec<(Column, Column)>, join_type: JoinType,
+                  schema: NaiveSchema) -> PhysicalPlanRef {
+        Arc::new(Self { left, right, on, join_type, schema, ctx })
+    }
+}
+impl GpuExec for GpuHashOuterJoin {
+    fn execute_device(&self) -> Result<Vec<GpuBatch>> {
+        let (lc, rc) = self.on.first().ok_or_else(|| ErrorCode::PlanError("Inner Join on Conditions can't not be empty".to_string()))?;
+        let (keep_probe, with_marks) = match self.join_type {
+            JoinType::Inner => (false, false), JoinType::Left => (false, true), JoinType::Right => (true, false),
+            JoinType::Cross => return Err(ErrorCode::PlanError("HashOuterJoin: the join type must be Inner, Left or Right".to_string())),
+        };
+        let left = child_device(&self.ctx, &self.left)?;
+        if left.is_empty() { return Err(ErrorCode::NotSupported("join with no left batches".to_string())); }
+        let single = self.ctx.concat(&left)?; // concat_batches (:132)
+        let lk = self.left.schema().index_of(&lc.name)? as i32; // by NAME, first match (:134-136)
+        let rk = self.right.schema().index_of(&rc.name)? as i32;
+        let mut jt = std::ptr::null_mut();
+        self.ctx.check(unsafe { nqe_hash_join_build(self.ctx.0, single.table.0, lk, &mut jt) })?;
+        let jt = GpuJoinTable(jt);
+        let mut mk = std::ptr::null_mut();
+        if with_marks { self.ctx.check(unsafe { nqe_join_marks_create(self.ctx.0, jt.0, &mut mk) })?; }
+        let marks = GpuJoinMarks(mk); // (a null handle is released as a no-op)
+        let flags = if keep_probe { NQE_JOIN_KEEP_PROBE } else { 0 };
+        let mut out = vec![];
+        for b in child_device(&self.ctx, &self.right)?.iter() { // one output batch per probe batch
+            let mut t = std::ptr::null_mut();
+            let st = unsafe {
+                match self.join_type {
+                    JoinType::Inner => nqe_hash_join_probe(self.ctx.0, jt.0, b.table.0, rk, &mut t), // the stateless inner join, fused tiers included
+                    _ => nqe_hash_join_probe_outer(self.ctx.0, jt.0, b.table.0, rk, flags, marks.0, &mut t),
+                }
+            };
+            self.ctx.check(st)?;
+            out.push(GpuBatch::wrap(t));
+        }
+        if with_marks { // the build rows no probe batch matched; dtypes from the probe child's schema
+            let dts: Vec<i32> = self.right.schema().fields().iter().map(|f| match f.data_type() {
+                DataType::Boolean => NQE_BOOLEAN, DataType::Int64 => NQE_INT64, DataType::UInt64 => NQE_UINT64,
+                DataType::Float64 => NQE_FLOAT64, DataType::Utf8 => NQE_UTF8, _ => -1, // → NQE_ERR_INVALID_ARGUMENT
+            }).collect();
+            let mut t = std::ptr::null_mut();
+            self.ctx.check(unsafe { nqe_hash_join_unmatched_build(self.ctx.0, jt.0, marks.0, dts.as_ptr(), dts.len() as i32, &mut t) })?;
+            out.push(GpuBatch::wrap(t));
+        }
+        drop(marks); // before the join table it is bound to
+        Ok(out)
+    }
+}
+impl PhysicalPlan for GpuHashOuterJoin {
     fn schema(&self) -> &NaiveSchema { &self.schema }
     fn children(&self) -> Result<Vec<PhysicalPlanRef>> { Ok(vec![self.left.clone(), self.right.clone()]) }
     fn execute(&self) -> Result<Vec<RecordBatch>> { self.ctx.download_all(&self.execute_device()?, &self.schema) }

@@ -28,7 +28,8 @@ SYMBOLS = [
     "nqe_table_unpack_words", "nqe_csv_infer_schema", "nqe_csv_read", "nqe_expr_evaluate",
     "nqe_filter", "nqe_selection_execute", "nqe_projection_execute", "nqe_selection_projection_execute",
     "nqe_aggregate_execute", "nqe_aggregate_partial", "nqe_aggregate_merge", "nqe_aggregate_merge_packed", "nqe_hash_join_execute",
-    "nqe_hash_join_build", "nqe_hash_join_probe", "nqe_join_table_release", "nqe_cross_join_execute", "nqe_nested_loop_join_execute", "nqe_sort_execute", "nqe_take", "nqe_synth_fill",
+    "nqe_hash_join_build", "nqe_hash_join_probe", "nqe_join_table_release", "nqe_join_marks_create", "nqe_join_marks_release",
+    "nqe_hash_join_probe_outer", "nqe_hash_join_unmatched_build", "nqe_cross_join_execute", "nqe_nested_loop_join_execute", "nqe_sort_execute", "nqe_take", "nqe_synth_fill",
     "nqe_device_alloc", "nqe_device_free",
     "nqe_comm_get_unique_id", "nqe_comm_rccl_version", "nqe_comm_create", "nqe_comm_create_custom", "nqe_comm_create_p2p", "nqe_comm_destroy", "nqe_comm_rank",
     "nqe_comm_world", "nqe_table_all_gather", "nqe_sharded_aggregate_execute", "nqe_sharded_hash_join_probe",
@@ -135,6 +136,10 @@ def lib():
         "nqe_hash_join_build": (i32, [vp, vp, i32, pvp]),
         "nqe_hash_join_probe": (i32, [vp, vp, vp, i32, pvp]),
         "nqe_join_table_release": (i32, [vp]),
+        "nqe_join_marks_create": (i32, [vp, vp, pvp]),
+        "nqe_join_marks_release": (i32, [vp]),
+        "nqe_hash_join_probe_outer": (i32, [vp, vp, vp, i32, C.c_uint32, vp, pvp]),
+        "nqe_hash_join_unmatched_build": (i32, [vp, vp, vp, C.POINTER(i32), i32, pvp]),
         "nqe_cross_join_execute": (i32, [vp, vp, vp, pvp]),
         "nqe_nested_loop_join_execute": (i32, [vp, vp, vp, i32, i32, pvp]),
         "nqe_sort_execute": (i32, [vp, vp, C.POINTER(NqeSortKey), i32, i64, pvp]),
@@ -166,6 +171,7 @@ def lib():
 
 
 TABLE_IMMUTABLE = 1  # NQE_TABLE_IMMUTABLE
+JOIN_KEEP_PROBE = 1  # NQE_JOIN_KEEP_PROBE
 
 
 class Context:
@@ -390,6 +396,27 @@ class Context:
         h = C.c_void_p()
         self.check(lib().nqe_hash_join_probe(self.handle, jt.handle, right.handle, right_key, C.byref(h)))
         return Table(self, h, derived_from=(right,))
+
+    def join_marks(self, jt: "JoinTable") -> "JoinMarks":
+        """nqe_join_marks_create: an empty record of which build rows of `jt` have matched (quirk Q19)"""
+        h = C.c_void_p()
+        self.check(lib().nqe_join_marks_create(self.handle, jt.handle, C.byref(h)))
+        return JoinMarks(self, h, jt)
+
+    def hash_join_probe_outer(self, jt: "JoinTable", right: "Table", right_key: int, keep_probe: bool = False, marks: Optional["JoinMarks"] = None) -> "Table":
+        """HashJoin honouring join_type for one probe batch (quirk Q19): the inner join's rows in its order; `keep_probe`: a probe row
+        without a match emits one row with every left column NULL; `marks`: records the build rows that matched"""
+        h = C.c_void_p()
+        self.check(lib().nqe_hash_join_probe_outer(self.handle, jt.handle, right.handle, right_key, JOIN_KEEP_PROBE if keep_probe else 0,
+                                                   marks.handle if marks is not None else None, C.byref(h)))
+        return Table(self, h)
+
+    def hash_join_unmatched_build(self, jt: "JoinTable", marks: Optional["JoinMarks"], right_dtypes: Sequence[int]) -> "Table":
+        """the build rows that `marks` has not seen match, in ascending build row, followed by one all-NULL column per dtype"""
+        da = (C.c_int32 * max(1, len(right_dtypes)))(*[int(d) for d in right_dtypes])
+        h = C.c_void_p()
+        self.check(lib().nqe_hash_join_unmatched_build(self.handle, jt.handle, marks.handle if marks is not None else None, da, len(right_dtypes), C.byref(h)))
+        return Table(self, h)
 
     def cross_join(self, left: "Table", right: "Table") -> "Table":
         """CrossJoin::execute for one batch pair (quirk Q15): left[j % L] beside right[j % R] for j < L*R, no validity"""
@@ -675,6 +702,20 @@ class JoinTable:
     def __del__(self):
         if getattr(self, "handle", None) and self.handle.value and _lib is not None and self.ctx.handle:
             _lib.nqe_join_table_release(self.handle)
+        self.handle = None
+
+
+class JoinMarks:
+    """nqe_join_marks: which build rows of one join table have matched so far (keeps the join table alive)"""
+
+    def __init__(self, ctx: Context, handle, jt: JoinTable):
+        self.ctx = ctx
+        self.handle = handle
+        self.join_table = jt
+
+    def __del__(self):
+        if getattr(self, "handle", None) and self.handle.value and _lib is not None and self.ctx.handle:
+            _lib.nqe_join_marks_release(self.handle)
         self.handle = None
 
 

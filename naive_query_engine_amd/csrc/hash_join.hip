@@ -32,7 +32,15 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "hash_join_probe_kernels.hpp" // (and through it hash_join_build_kernels.hpp, hash_join_table.hpp)
+#include "hash_join_outer_kernels.hpp" // (and through it hash_join_probe_kernels.hpp, hash_join_build_kernels.hpp, hash_join_table.hpp)
+
+// which build rows have matched so far (quirk Q19): bit `start` per matched key, left_rows bits in 32-bit words, bound to one join table
+struct nqe_join_marks {
+    nqe_ctx *ctx = nullptr;
+    const nqe_join_table *table = nullptr;
+    int64_t rows = 0;
+    nqe::BufRef bits;
+};
 
 namespace nqe {
 
@@ -965,6 +973,216 @@ std::unique_ptr<nqe_table> probe_duplicates(nqe_ctx *ctx, const nqe_join_table *
     return out;
 }
 
+// ---- outer joins (quirk Q19): HashJoin honouring join_type.  ONE general path over every build form — lookup_of(jt) is complete for
+// all of them (`dense` or `slots` is always filled) — that takes none of the fused one-pass tiers: count pass (outer_count_kernel),
+// scan, output-driven write pass (outer_write_kernel), and for the build-preserving side a pass over the build rows
+// (unmatched_build_kernel) + compaction.  The match relation is the inner join's, Q11 included.
+// exact null counts of the nullable columns of `out` (count_set_bits_kernel per column, one read-back for all of them)
+void count_nulls_exact(nqe_ctx *ctx, nqe_table *out) {
+    std::vector<size_t> which;
+    for (size_t c = 0; c < out->cols.size(); ++c)
+        if (out->cols[c].validity && out->cols[c].null_count < 0) which.push_back(c);
+    if (which.empty()) return;
+    if (out->rows == 0) {
+        for (size_t c : which) out->cols[c].null_count = 0;
+        return;
+    }
+    BufRef set = dev_alloc_zero(ctx, which.size() * 8);
+    for (size_t k = 0; k < which.size(); ++k)
+        launch(ctx, "join_outer_null_count", count_set_bits_kernel, dim3(stream_grid(ctx, (out->rows + 63) / 64, 256)), dim3(256), 0,
+               (const uint64_t *)out->cols[which[k]].validity->ptr, out->rows, (unsigned long long *)set->ptr + k);
+    std::vector<unsigned long long> h(which.size());
+    NQE_HIP_CHECK(hipMemcpyAsync(h.data(), set->ptr, which.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    sync(ctx);
+    for (size_t k = 0; k < which.size(); ++k) out->cols[which[k]].null_count = out->rows - int64_t(h[k]);
+}
+// pass 2 of the outer probe and what follows it (cf. write_duplicate_matches): a left column gets a validity buffer when its source
+// has one or the batch holds a NULL-extended row (`has_null`)
+void write_outer_matches(nqe_ctx *ctx, const nqe_join_table *jt, const nqe_table *right, int64_t M, bool has_null, const BufRef &pmeta, const BufRef &offs, int grid,
+                         const std::vector<const DevColumn *> &srcs, const std::vector<int> &out_slot, OuterCols &oc, nqe_table *out) {
+    const int64_t n = right->rows;
+    const size_t nleft = jt->left_cols.size();
+    DevColumn outer_pos, inner_pos;
+    out->cols.resize(nleft + right->cols.size());
+    std::vector<BufRef> bool_bytes(srcs.size()), valid_bytes(srcs.size());
+    std::vector<DevColumn> dsts(srcs.size());
+    bool all_plain = true;
+    for (size_t k = 0; k < srcs.size(); ++k) {
+        const DevColumn &src = *srcs[k];
+        const bool left = int(k) < oc.n_left;
+        const bool rowid = out_slot[k] < 0; // outer_pos / inner_pos: the NULL of a take index is -1, not a validity bit
+        const bool v = src.validity != nullptr || (left && has_null && !rowid);
+        DevColumn dst = src.dtype == NQE_BOOLEAN ? make_bool_column(ctx, M, v) : make_word_column(ctx, src.dtype, M, v);
+        oc.src[k] = src.values ? src.values->ptr : nullptr;
+        oc.src_valid[k] = src.valid();
+        oc.dtype[k] = src.dtype;
+        oc.null_word[k] = rowid ? ~0ull : 0ull;
+        if (src.dtype == NQE_BOOLEAN) {
+            bool_bytes[k] = dev_alloc(ctx, size_t(M) + 8);
+            oc.dst_bool_bytes[k] = (uint8_t *)bool_bytes[k]->ptr;
+        } else {
+            oc.dst_words[k] = (uint64_t *)dst.values->ptr;
+        }
+        if (v) {
+            valid_bytes[k] = dev_alloc(ctx, size_t(M) + 8);
+            oc.dst_valid_bytes[k] = (uint8_t *)valid_bytes[k]->ptr;
+        }
+        all_plain = all_plain && is_plain_word(src);
+        dsts[k] = std::move(dst);
+    }
+    if (n && M)
+        launch(ctx, "join_outer_write", all_plain ? outer_write_kernel<true> : outer_write_kernel<false>, dim3(grid), dim3(JT_BLOCK), 0, (const uint64_t *)pmeta->ptr, n,
+               (const uint64_t *)offs->ptr, jt->perm ? (const uint32_t *)jt->perm->ptr : (const uint32_t *)nullptr, jt->direct ? 1 : 0, oc);
+    for (size_t k = 0; k < srcs.size(); ++k) {
+        if (bool_bytes[k]) pack_bytes_to_bits(ctx, (const uint8_t *)bool_bytes[k]->ptr, M, (uint64_t *)dsts[k].values->ptr);
+        if (valid_bytes[k]) pack_bytes_to_bits(ctx, (const uint8_t *)valid_bytes[k]->ptr, M, (uint64_t *)dsts[k].validity->ptr);
+        if (out_slot[k] >= 0) out->cols[size_t(out_slot[k])] = dsts[k];
+        else if (out_slot[k] == -1) outer_pos = dsts[k];
+        else inner_pos = dsts[k];
+    }
+    for (size_t c = 0; c < nleft; ++c)
+        if (jt->left_cols[c].dtype == NQE_UTF8) out->cols[c] = take_utf8(ctx, jt->left_cols[c], (const int64_t *)outer_pos.words(), M, has_null);
+    for (size_t c = 0; c < right->cols.size(); ++c)
+        if (right->cols[c].dtype == NQE_UTF8) out->cols[nleft + c] = take_utf8(ctx, right->cols[c], (const int64_t *)inner_pos.words(), M, false);
+    count_nulls_exact(ctx, out);
+}
+// `marks`: the bitmap of nqe_join_marks (bit `start` per matched key), or null
+std::unique_ptr<nqe_table> probe_outer(nqe_ctx *ctx, const nqe_join_table *jt, const nqe_table *right, int right_key, bool keep_probe, uint32_t *marks) {
+    if (right_key < 0 || size_t(right_key) >= right->cols.size()) fail(NQE_ERR_LOGICAL, "ColumnExpr must has name or idx");
+    const DevColumn &rk_orig = right->cols[size_t(right_key)];
+    check_key_types(jt->key_dtype, rk_orig.dtype);
+    if (jt->left_cols.size() + right->cols.size() > size_t(MAX_JOIN_COLS)) fail(NQE_ERR_NOT_SUPPORTED, "join output wider than 32 columns");
+    if (keep_probe && jt->left_rows > int64_t(OUTER_NULL_START)) fail(NQE_ERR_NOT_SUPPORTED, "outer join: a build side of 2^32 rows collides with the no-match mark");
+    DevColumn rk_codes;
+    if (rk_orig.dtype == NQE_UTF8) rk_codes = utf8_encode_probe(ctx, rk_orig, jt->dict);
+    const DevColumn &rk = rk_orig.dtype == NQE_UTF8 ? rk_codes : rk_orig;
+    const int64_t n = right->rows;
+    const int64_t ntiles = (n + JT_ROWS - 1) / JT_ROWS;
+    BufRef pmeta = dev_alloc(ctx, size_t(n) * 8 + 8);
+    BufRef counts = dev_alloc(ctx, size_t(ntiles + 1) * 4);
+    BufRef offs = dev_alloc(ctx, size_t(ntiles + 1) * 8);
+    BufRef misses = dev_alloc_zero(ctx, 8);
+    const int grid = int(std::max<int64_t>(1, std::min<int64_t>(ntiles, int64_t(ctx->num_cus) * 8)));
+    if (n) {
+        auto k = keep_probe ? (marks ? outer_count_kernel<true, true> : outer_count_kernel<true, false>) : (marks ? outer_count_kernel<false, true> : outer_count_kernel<false, false>);
+        launch(ctx, "join_outer_count", k, dim3(grid), dim3(JT_BLOCK), 0, rk.words(), n, lookup_of(jt), (uint64_t *)pmeta->ptr, (uint32_t *)counts->ptr, marks,
+               (unsigned long long *)misses->ptr, ctx->d_flags);
+    }
+    exclusive_scan_u32_to_u64(ctx, (const uint32_t *)counts->ptr, (uint64_t *)offs->ptr, ntiles);
+    const int64_t M = int64_t(read_scalar(ctx, (const uint64_t *)offs->ptr + ntiles));
+    const bool has_null = keep_probe && read_scalar(ctx, (const unsigned long long *)misses->ptr) != 0ull;
+    {
+        int f[NQE_NUM_FLAGS];
+        flags_read(ctx, f);
+        if (f[NQE_FLAG_TABLE_FULL]) fail(NQE_ERR_OUT_OF_MEMORY, "join output of one probe tile exceeds 2^32 rows");
+    }
+    auto out = std::make_unique<nqe_table>();
+    out->ctx = ctx;
+    out->rows = M;
+    // the kernel's columns: left columns, right columns; a Utf8 column goes through a row-number column (outer_pos / inner_pos) and the
+    // Utf8 `take`.  A plain integer build key is taken from the probe side at the probe row (the key of a match is bit-identical on both
+    // sides; a NULL-extended row gets 0 under a NULL all the same), and in a batch without NULL-extended rows the two key columns of the
+    // output are ONE buffer, as in the inner join
+    bool utf8_left = false, utf8_right = false;
+    for (auto &c : jt->left_cols) utf8_left |= c.dtype == NQE_UTF8;
+    for (auto &c : right->cols) utf8_right |= c.dtype == NQE_UTF8;
+    OuterCols oc;
+    std::memset(&oc, 0, sizeof(oc));
+    DevColumn left_rowid, right_rowid, key_from_probe;
+    std::vector<const DevColumn *> srcs;
+    std::vector<int> out_slot;
+    const bool key_shortcut = jt->key_dtype != NQE_UTF8 && !jt->left_cols[size_t(jt->left_key)].validity;
+    const bool key_shared = key_shortcut && !has_null && share_key_column(jt->left_cols[size_t(jt->left_key)], rk_orig);
+    for (size_t c = 0; c < jt->left_cols.size(); ++c) {
+        if (jt->left_cols[c].dtype == NQE_UTF8 || (key_shared && int(c) == jt->left_key)) continue;
+        if (key_shortcut && int(c) == jt->left_key) {
+            key_from_probe = as_build_key(rk);
+            key_from_probe.dtype = jt->left_cols[c].dtype;
+            oc.from_probe[srcs.size()] = 1;
+            srcs.push_back(&key_from_probe);
+        } else
+            srcs.push_back(&jt->left_cols[c]);
+        out_slot.push_back(int(c));
+    }
+    if (utf8_left) {
+        left_rowid = rowid_column(ctx, jt->left_rows);
+        srcs.push_back(&left_rowid); out_slot.push_back(-1);
+    }
+    oc.n_left = int(srcs.size());
+    for (size_t c = 0; c < right->cols.size(); ++c)
+        if (right->cols[c].dtype != NQE_UTF8) { srcs.push_back(&right->cols[c]); out_slot.push_back(int(jt->left_cols.size() + c)); }
+    if (utf8_right) {
+        right_rowid = rowid_column(ctx, n);
+        srcs.push_back(&right_rowid); out_slot.push_back(-2);
+    }
+    oc.n = int(srcs.size());
+    // left columns with a copy in sorted-row order are read at start + match number (see probe_duplicates)
+    std::vector<DevColumn> by_pos_cols(size_t(oc.n_left));
+    for (int k = 0; k < oc.n_left; ++k) {
+        const int ci = out_slot[size_t(k)];
+        if (oc.from_probe[k]) continue;
+        if (!jt->direct && ci >= 0 && size_t(ci) < jt->sorted_cols.size() && jt->sorted_cols[size_t(ci)]) {
+            by_pos_cols[size_t(k)] = *srcs[size_t(k)];
+            by_pos_cols[size_t(k)].values = jt->sorted_cols[size_t(ci)];
+            srcs[size_t(k)] = &by_pos_cols[size_t(k)];
+            oc.by_pos[k] = 1;
+        } else
+            oc.need_perm = 1;
+    }
+    write_outer_matches(ctx, jt, right, M, has_null, pmeta, offs, grid, srcs, out_slot, oc, out.get());
+    if (key_shared) {
+        out->cols[size_t(jt->left_key)] = out->cols[jt->left_cols.size() + size_t(right_key)];
+        out->cols[size_t(jt->left_key)].dtype = jt->left_cols[size_t(jt->left_key)].dtype;
+    }
+    sync(ctx); // the temporaries above are released on return
+    return out;
+}
+// m rows of NULL: zero words / false bits / zero-length strings under an all-zero validity buffer (none at 0 rows: no NULL-extended row)
+DevColumn null_column(nqe_ctx *ctx, int dtype, int64_t m) {
+    DevColumn c;
+    c.dtype = dtype;
+    c.length = m;
+    if (dtype == NQE_UTF8) {
+        c.values = dev_alloc_zero(ctx, size_t(m + 1) * 4 + 8);
+        c.data = dev_alloc(ctx, 8);
+    } else if (dtype == NQE_BOOLEAN) {
+        c.values = dev_alloc_zero(ctx, bitmap_alloc_bytes(m));
+    } else {
+        c.values = dev_alloc_zero(ctx, size_t(m) * 8);
+    }
+    if (m) {
+        c.validity = dev_alloc_zero(ctx, bitmap_alloc_bytes(m));
+        c.null_count = m;
+    }
+    return c;
+}
+// the build rows whose bit is not set, in ascending build row, every right column NULL
+std::unique_ptr<nqe_table> unmatched_build(nqe_ctx *ctx, const nqe_join_table *jt, const uint32_t *marks, const int32_t *right_dtypes, int num_right) {
+    if (jt->left_cols.size() + size_t(num_right) > size_t(MAX_JOIN_COLS)) fail(NQE_ERR_NOT_SUPPORTED, "join output wider than 32 columns");
+    const int64_t n = jt->left_rows;
+    DevColumn codes;
+    const uint64_t *bkeys = nullptr;
+    if (!jt->direct) { // duplicate keys: the row's own key finds the bit its key group shares
+        const DevColumn &kc = jt->left_cols[size_t(jt->left_key)];
+        if (kc.dtype == NQE_UTF8) codes = utf8_encode_probe(ctx, kc, jt->dict);
+        bkeys = kc.dtype == NQE_UTF8 ? codes.words() : kc.words();
+    }
+    BufRef counts;
+    KeepMask km = new_keep_mask(ctx, n, &counts);
+    if (km.ntiles)
+        launch(ctx, "join_outer_unmatched", unmatched_build_kernel, dim3(stream_grid(ctx, km.ntiles, 4)), dim3(256), 0, bkeys, n, km.ntiles, lookup_of(jt), marks,
+               (uint64_t *)km.keep->ptr, (uint32_t *)counts->ptr);
+    km = finish_mask(ctx, km, counts);
+    auto out = std::make_unique<nqe_table>();
+    out->ctx = ctx;
+    out->rows = km.total;
+    for (auto &c : jt->left_cols) out->cols.push_back(compact_column(ctx, c, km));
+    for (int k = 0; k < num_right; ++k) out->cols.push_back(null_column(ctx, right_dtypes[k], km.total));
+    count_nulls_exact(ctx, out.get());
+    sync(ctx);
+    return out;
+}
+
 std::unique_ptr<nqe_table> probe_table(nqe_ctx *ctx, const nqe_join_table *jt, const nqe_table *right, int right_key) {
     if (right_key < 0 || size_t(right_key) >= right->cols.size()) fail(NQE_ERR_LOGICAL, "ColumnExpr must has name or idx");
     const DevColumn &rk_orig = right->cols[size_t(right_key)];
@@ -1008,6 +1226,52 @@ nqe_status nqe_hash_join_probe(nqe_ctx *ctx, const nqe_join_table *build, const 
 nqe_status nqe_join_table_release(nqe_join_table *jt) {
     delete jt;
     return NQE_OK;
+}
+
+nqe_status nqe_join_marks_create(nqe_ctx *ctx, const nqe_join_table *build, nqe_join_marks **out) {
+    NQE_API_BEGIN(ctx)
+    if (!ctx || !build || !out || build->ctx != ctx) fail(NQE_ERR_INVALID_ARGUMENT, "bad arguments");
+    auto m = std::make_unique<nqe_join_marks>();
+    m->ctx = ctx;
+    m->table = build;
+    m->rows = build->left_rows;
+    m->bits = dev_alloc_zero(ctx, size_t((build->left_rows + 31) / 32) * 4 + 8);
+    *out = m.release();
+    NQE_API_END()
+}
+
+nqe_status nqe_join_marks_release(nqe_join_marks *marks) {
+    delete marks;
+    return NQE_OK;
+}
+
+nqe_status nqe_hash_join_probe_outer(nqe_ctx *ctx, const nqe_join_table *build, const nqe_table *right, int32_t right_key, uint32_t flags,
+                                     nqe_join_marks *marks, nqe_table **out) {
+    NQE_API_BEGIN(ctx)
+    if (!ctx || !build || !right || !out) fail(NQE_ERR_INVALID_ARGUMENT, "bad arguments");
+    if (flags & ~NQE_JOIN_KEEP_PROBE) fail(NQE_ERR_INVALID_ARGUMENT, "nqe_hash_join_probe_outer: unknown flag bits");
+    if (marks && (marks->ctx != ctx || marks->table != build || marks->rows != build->left_rows))
+        fail(NQE_ERR_INVALID_ARGUMENT, "nqe_hash_join_probe_outer: the marks belong to another join table or context");
+    flags_reset(ctx);
+    *out = probe_outer(ctx, build, right, right_key, (flags & NQE_JOIN_KEEP_PROBE) != 0, marks ? (uint32_t *)marks->bits->ptr : (uint32_t *)nullptr).release();
+    NQE_API_END()
+}
+
+nqe_status nqe_hash_join_unmatched_build(nqe_ctx *ctx, const nqe_join_table *build, const nqe_join_marks *marks, const int32_t *right_dtypes,
+                                         int32_t num_right, nqe_table **out) {
+    NQE_API_BEGIN(ctx)
+    if (!ctx || !build || !out) fail(NQE_ERR_INVALID_ARGUMENT, "bad arguments");
+    if (!marks) fail(NQE_ERR_INVALID_ARGUMENT, "nqe_hash_join_unmatched_build: marks are required");
+    if (marks->ctx != ctx || marks->table != build || marks->rows != build->left_rows)
+        fail(NQE_ERR_INVALID_ARGUMENT, "nqe_hash_join_unmatched_build: the marks belong to another join table or context");
+    if (num_right < 0 || (num_right > 0 && !right_dtypes)) fail(NQE_ERR_INVALID_ARGUMENT, "nqe_hash_join_unmatched_build: bad right_dtypes");
+    for (int32_t k = 0; k < num_right; ++k) {
+        if (right_dtypes[k] < NQE_NULLTYPE || right_dtypes[k] > NQE_UTF8) fail(NQE_ERR_INVALID_ARGUMENT, "nqe_hash_join_unmatched_build: a dtype outside nqe_dtype");
+        if (right_dtypes[k] == NQE_NULLTYPE) fail(NQE_ERR_NOT_SUPPORTED, "nqe_hash_join_unmatched_build: no column of DataType::Null");
+    }
+    flags_reset(ctx);
+    *out = unmatched_build(ctx, build, (const uint32_t *)marks->bits->ptr, right_dtypes, num_right).release();
+    NQE_API_END()
 }
 
 nqe_status nqe_hash_join_execute(nqe_ctx *ctx, const nqe_table *left, const nqe_table *right, int32_t left_key,

@@ -464,6 +464,60 @@ class HashJoin(PhysicalPlan):
         return out
 
 
+# ----------------------------------------------------------------------------- outer hash join
+class HashOuterJoin(PhysicalPlan):
+    """HashJoin honouring `join_type` (quirk Q19; the reference's HashJoin stores the type and never reads it).  The match relation
+    is HashJoin's, Q11 included: LEFT child = build side, RIGHT = probe side, only on[0], key validity ignored.  Inner: the inner
+    join.  Right: one output batch per probe batch; a probe row without a match emits one row with every left column NULL.  Left:
+    the probe batches' outputs are the inner join's, and one final batch — always emitted, possibly with 0 rows — holds the build
+    rows that matched in no probe batch, in ascending build row, with every right column NULL.  Cross raises PlanError.  Nothing
+    is kept between execute() calls (no Q11 re-execution duplication)."""
+
+    def __init__(self, left, right, on, join_type, schema):
+        self.left, self.right, self.on, self.join_type, self._schema = left, right, list(on), join_type, list(schema)
+
+    @staticmethod
+    def create(left: PhysicalPlan, right: PhysicalPlan, on: Sequence[Tuple[ColumnRef, ColumnRef]], join_type, schema: NaiveSchema) -> "HashOuterJoin":
+        return HashOuterJoin(left, right, on, join_type, schema)
+
+    def schema(self):
+        return self._schema
+
+    def children(self):
+        return [self.left, self.right]
+
+    def execute(self):
+        if not self.on:  # as HashJoin (hash_join.rs:125-129)
+            raise ErrorCode(Status.PlanError, "Inner Join on Conditions can't not be empty")
+        if self.join_type not in (JoinType.Inner, JoinType.Left, JoinType.Right):
+            raise ErrorCode(Status.PlanError, "HashOuterJoin: the join type must be Inner, Left or Right")
+        lb = self.left.execute()
+        rb = self.right.execute()
+        ctx = _ctx_of(lb or rb)
+        if not lb:
+            raise ErrorCode(Status.NotSupported, "join with an empty left batch list is not supported on the device path")
+        ltab = lb[0].table if len(lb) == 1 else ctx.concat([b.table for b in lb])  # concat_batches (:132)
+        lkey = ColumnExpr.try_create(self.on[0][0].name, None).resolve(lb[0].fields)  # by NAME, first match (:134-136)
+        jt = ctx.hash_join_build(ltab, lkey)
+        marks = ctx.join_marks(jt) if self.join_type == JoinType.Left else None
+        ncols = len(lb[0].fields) + len(self.right.schema())
+        out = []
+        for b in rb:  # one output batch per probe batch
+            rkey = ColumnExpr.try_create(self.on[0][1].name, None).resolve(b.fields)
+            if self.join_type == JoinType.Inner:
+                t = ctx.hash_join_probe(jt, b.table, rkey)
+            else:
+                t = ctx.hash_join_probe_outer(jt, b.table, rkey, keep_probe=self.join_type == JoinType.Right, marks=marks)
+            fields = self._schema if len(self._schema) == t.num_columns else list(lb[0].fields) + list(b.fields)
+            out.append(DeviceRecordBatch(fields, t))
+        if self.join_type == JoinType.Left:  # the build rows no probe batch matched; dtypes from the probe child's schema
+            rfields = list(rb[0].fields) if rb else list(self.right.schema())
+            t = ctx.hash_join_unmatched_build(jt, marks, [f.dtype for f in rfields])
+            fields = self._schema if len(self._schema) == ncols else list(lb[0].fields) + rfields
+            out.append(DeviceRecordBatch(fields, t))
+        return out
+
+
 # ----------------------------------------------------------------------------- cross join
 class CrossJoin(PhysicalPlan):
     """src/physical_plan/cross_join.rs:26-192 — one output batch per (outer, inner) batch pair, outer-major; quirk Q15: with L and R

@@ -20,7 +20,7 @@ from __future__ import annotations
 from typing import Dict, List, Optional, Sequence
 
 from .arrow_host import ErrorCode, Field, RecordBatch, Status
-from .physical_plan import (CrossJoin, CsvConfig, CsvTable, DeviceRecordBatch, HashJoin, MemTable, NaiveSchema, NestedLoopJoin, PhysicalAggregatePlan, PhysicalLimitPlan,
+from .physical_plan import (CrossJoin, CsvConfig, CsvTable, DeviceRecordBatch, HashJoin, HashOuterJoin, MemTable, NaiveSchema, NestedLoopJoin, PhysicalAggregatePlan, PhysicalLimitPlan,
                             PhysicalOffsetPlan, PhysicalPlan, PhysicalSortPlan, ProjectionPlan, ScanPlan, SelectionPlan, _ctx_of, _Materialized)
 
 
@@ -115,6 +115,8 @@ def rewrite(plan: PhysicalPlan) -> PhysicalPlan:
         return PhysicalSortPlan.create(rewrite(plan.input), plan.sort_exprs, plan.fetch)
     if isinstance(plan, PhysicalOffsetPlan):
         return PhysicalOffsetPlan.create(rewrite(plan.input), plan.n)
+    if isinstance(plan, HashOuterJoin):
+        return HashOuterJoin.create(rewrite(plan.left), rewrite(plan.right), plan.on, plan.join_type, plan._schema)
     if isinstance(plan, HashJoin):
         return HashJoin.create(rewrite(plan.left), rewrite(plan.right), plan.on, plan.join_type, plan._schema)
     if isinstance(plan, CrossJoin):
