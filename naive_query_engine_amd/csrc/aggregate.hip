@@ -1,24 +1,25 @@
-// aggregate.hip — PhysicalAggregatePlan::execute (reference: src/physical_plan/aggregate/mod.rs:113-222,
-// group split :54-102, operators aggregate/{sum,avg,count,max,min}.rs) fused with the SelectionPlan
-// below it and the key expression group_expr[0].
+// aggregate.hip — PhysicalAggregatePlan::execute (reference: src/physical_plan/aggregate/mod.rs:113-222, group split :54-102, operators
+// aggregate/{sum,avg,count,max,min}.rs) fused with the SelectionPlan below it and the key expression group_expr[0]: the HOST side of the
+// operator, and the C ABI of include/nqe.h for it.  One translation unit (aggregate.o); the kernels it launches live in
+//   aggregate_kernels.hpp      the general grouped kernel, the un-grouped kernels and their fold (this unit's own; included below)
+//   aggregate_fast_kernel.hpp  the streaming kernel with its workgroup LDS table (instances: aggregate_fast.hip, aggregate_fast_inst.hip)
+//   aggregate_tiny.hip         the register-resident kernel for `col % m`, m <= 4
+//   aggregate_partition.hip    the partitioned path: slab scatter, exact count / scan / scatter, segments, sub-partitions
+//   aggregate_tail.hip         key sample and key range, table initialisation, the tails (rank, collect, dense rank, range emit), the merges
+// Map of this file:
+//   TableBufs / make_table, AggPlan / plan_aggs, alloc_outputs, emit_ranked / emit   the group table, the aggregate list, the tails' launches
+//   the constants of the tiers (what the A/B runs settled)
+//   AggRun                     one object per execution — plan, execute, react; its comment is the map of the tier ladder
+//   run_aggregate              prepare -> size_tables -> load_hints -> sample_keys -> pick_key_range -> run
+//   extern "C"                 nqe_aggregate_execute, nqe_aggregate_partial, nqe_aggregate_merge, nqe_aggregate_merge_packed
+// What a context remembers of a query shape between executions is aggregate_memo.hpp (nqe_ctx::agg_memo); AggRun reads and writes it
+// through recall_memo() and memo().
 //
-// The reference concatenates the input, materialises the key column, builds
-// HashMap<key, Vec<row>> and then calls a virtual update(batch, idx) per row per aggregate.
-// Here ONE streaming kernel reads each referenced column exactly once (coalesced, all loads of
-// an iteration issued before first use), evaluates predicate and key in registers, and
-// accumulates {count, sum, min, max} per (group, value column) in a per-workgroup LDS hash
-// table (open addressing, Fibonacci hash, 64-bit CAS on the key, LDS atomics on the state).
-// Rows whose key does not fit the workgroup table go straight to the global table.  At the end
-// every workgroup merges its LDS table into the global open-addressing table with device-scope
-// atomics; a collect + sort-by-key + finalize tail emits one row per group.
-//
-// Algorithmic HBM bytes per row = 8 B per distinct referenced column (16 B/row for
-// `... from t where id < K group by id % 1024` with count/sum/avg/min/max over v).
-//
-// Semantics kept from the reference (quirk Q10): all accumulation in f64 (`val as f64`), count =
-// non-null values, max starts at f64::MIN, min at f64::MAX, OrderedFloat NaN ordering (max → NaN
-// if any NaN, min ignores NaN), NULL keys dropped, NULL-predicate rows contribute nothing.
-// Sum order differs from the reference's sequential row order (atomics): ≤1e-9 relative.
+// Semantics kept from the reference (quirk Q10): all accumulation in f64 (`val as f64`), count = non-null values, max starts at f64::MIN,
+// min at f64::MAX, OrderedFloat NaN ordering (max → NaN if any NaN, min ignores NaN), NULL keys dropped, NULL-predicate rows contribute
+// nothing.  Sum order differs from the reference's sequential row order (atomics, folds): ≤1e-9 relative.
+// Algorithmic HBM bytes per row = 8 B per distinct referenced column (16 B/row for `... from t where id < K group by id % 1024`
+// with count/sum/avg/min/max over v).
 #include <algorithm>
 #include <cmath>
 #include <cfloat>
@@ -34,449 +35,7 @@ namespace {
 
 using namespace agg;
 
-// ------------------------------------------------------------------ grouped kernel
-// History: with the 64-bit software divide inlined for predicate and key in each of the 4 unrolled rows the first
-// version of this kernel was 30k instructions long and instruction-fetch bound (2.2 TB/s).  Now literal divisors use
-// shift/mask or a magic multiply and only column÷column reaches the out-of-line divmod_general, so the general
-// SimpleExpr evaluator is inlined again; the common shapes are still specialised:
-//   PRED: 0 none | 1 `col cmp lit` (literal on either side, normalised on the host) | 2 Boolean bitmap
-//         | 3 any other SimpleExpr
-//   KEY : 0 plain column | 1 `col % ±2^k` | 2 any other SimpleExpr
-//   PLAIN: every streamed source is an 8-byte column without a validity bitmap (no bitmap loads)
-__device__ __forceinline__ bool cmp_lit(int op, int dt, uint64_t a, uint64_t b) {
-    bool lt, eq;
-    if (dt == NQE_INT64) { lt = (long long)a < (long long)b; eq = a == b; }
-    else if (dt == NQE_FLOAT64) { double x = u2d(a), y = u2d(b); lt = x < y; eq = x == y; if (x != x || y != y) return op == NQE_OP_NOT_EQ; }
-    else { lt = a < b; eq = a == b; }
-    return op == NQE_OP_EQ ? eq : op == NQE_OP_NOT_EQ ? !eq : op == NQE_OP_LT ? lt : op == NQE_OP_LT_EQ ? (lt || eq)
-           : op == NQE_OP_GT ? !(lt || eq) : !lt;
-}
-
-template <int PRED, int KEY, bool PLAIN>
-__global__ void __launch_bounds__(AGG_BLOCK) agg_grouped_kernel(AggArgs a, GroupTable g, int *flags) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const uint32_t cap = uint32_t(a.lds_cap);
-    const uint32_t slots = cap + 1;
-    uint64_t *lkeys = reinterpret_cast<uint64_t *>(smem);
-    const uint32_t nvl = a.nv > 0 ? uint32_t(a.nv) : 1u;                 // value columns of THIS pass
-    double *lsum = reinterpret_cast<double *>(lkeys + slots);            // [nvl][slots]
-    uint64_t *lmn = reinterpret_cast<uint64_t *>(lsum + nvl * slots);    // [nvl][slots]
-    uint64_t *lmx = lmn + nvl * slots;                                   // [nvl][slots]
-    uint32_t *lcnt = reinterpret_cast<uint32_t *>(lmx + nvl * slots);    // [nvl][slots]
-    const uint64_t ORD_MAX = f64_to_ord(DBL_MAX), ORD_MIN = f64_to_ord(-DBL_MAX);
-    __shared__ int lds_full_flag;
-    volatile int *lds_full = &lds_full_flag;
-    if (threadIdx.x == 0) lds_full_flag = 0;
-
-    for (uint32_t s = threadIdx.x; s < slots; s += blockDim.x) {
-        lkeys[s] = EMPTY_KEY;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            if (uint32_t(j) >= nvl) continue;
-            lsum[j * slots + s] = 0.0;
-            lmn[j * slots + s] = ORD_MAX;
-            lmx[j * slots + s] = ORD_MIN;
-            lcnt[j * slots + s] = 0;
-        }
-    }
-    __syncthreads();
-
-    // Per-thread run cache.  All rows a thread visits are congruent modulo blockDim (row = base + u*blockDim +
-    // tid with base a multiple of blockDim*AGG_U), so for clustered keys — and for `id % m` over a row-number id
-    // whenever m divides blockDim — consecutive rows of a thread carry the SAME key.  They are accumulated in
-    // registers and written to the workgroup table only when the key changes (one flush per run instead of four
-    // LDS atomics per row).  Random keys flush every row.
-    bool full = false; // register copy of lds_full_flag (set by own failures, refreshed per tile)
-    bool run_live = false;
-    uint64_t run_key = 0;
-    uint32_t rcnt[NV];
-    double rsum[NV];
-    uint64_t rmn[NV], rmx[NV];
-    bool rnan[NV];
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        rcnt[j] = 0; rsum[j] = 0.0; rmn[j] = ORD_MAX; rmx[j] = ORD_MIN; rnan[j] = false;
-    }
-    auto flush_run = [&]() {
-        // once this workgroup's table has rejected a key, later keys skip it: any split of the updates between
-        // the LDS table and the global table is correct (the merge is additive), and a full table costs 48 probes
-        int slot = full ? -1 : lds_find_or_insert(lkeys, run_key, cap, a.lds_shift);
-        if (slot < 0 && !full) {
-            full = true;
-            *lds_full = 1;
-        }
-        int64_t gslot = slot < 0 ? global_find_or_insert(g, run_key, flags) : 0;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            if (j >= a.nv) continue;
-            if (slot >= 0) {
-                uint32_t o = uint32_t(j) * slots + uint32_t(slot);
-                if (rcnt[j]) atomicAdd(&lcnt[o], rcnt[j]); // < 2^31 rows per workgroup, bit 31 is the NaN flag
-                if (rnan[j]) atomicOr(&lcnt[o], NAN_BIT);
-                if (a.need_sum[j] && rcnt[j]) unsafeAtomicAdd(&lsum[o], rsum[j]);
-                if (a.need_minmax[j]) {
-                    // read-before-atomic: once a group holds a few rows almost no run improves its extremes, and
-                    // an LDS read costs a small fraction of a 64-bit LDS atomic.  A stale read only causes a
-                    // redundant (still correct) atomic.
-                    if (rmn[j] < lmn[o]) atomicMin((unsigned long long *)&lmn[o], (unsigned long long)rmn[j]);
-                    if (rmx[j] > lmx[o]) atomicMax((unsigned long long *)&lmx[o], (unsigned long long)rmx[j]);
-                }
-            } else if (gslot >= 0) {
-                global_update(g, gslot, a.v0 + j, rcnt[j], rsum[j], a.need_sum[j] != 0, rmn[j], rmx[j], a.need_minmax[j] != 0,
-                              rnan[j]);
-            }
-            rcnt[j] = 0; rsum[j] = 0.0; rmn[j] = ORD_MAX; rmx[j] = ORD_MIN; rnan[j] = false;
-        }
-    };
-
-    const uint64_t *keyp = static_cast<const uint64_t *>(a.key_src.values);
-    const uint64_t *predp = static_cast<const uint64_t *>(a.pred_src.values);
-    const int pred_op = a.pred.op[0], pred_dt = a.pred.op_dtype[0];
-    const uint64_t pred_lit = a.pred.lit[0];
-    const uint64_t key_mask = a.key.aux[0].abs_lit - 1;
-    const bool key_signed = a.key.op_dtype[0] == NQE_INT64;
-
-    const int64_t step = int64_t(blockDim.x) * AGG_U;
-    for (int64_t base = int64_t(blockIdx.x) * step; base < a.n; base += int64_t(gridDim.x) * step) {
-        if (__hip_atomic_load(&flags[NQE_FLAG_TABLE_FULL], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break; // host retries
-        full = full || *lds_full != 0;
-        uint64_t kw[AGG_U], pw[AGG_U], vw[NV][AGG_U];
-        // ---- load phase: every referenced word of this iteration is requested before any use
-#pragma unroll
-        for (int u = 0; u < AGG_U; ++u) {
-            int64_t row = base + int64_t(u) * blockDim.x + threadIdx.x;
-            bool in = row < a.n;
-            if (PLAIN) {
-                kw[u] = in ? keyp[row] : 0;
-                pw[u] = ((PRED == 1 || PRED == 3) && in && !a.pred_shares_key) ? predp[row] : 0;
-            } else {
-                kw[u] = in ? load_word(a.key_src.values, a.key_src.dtype, row) : 0;
-                pw[u] = ((PRED == 1 || PRED == 3) && in && !a.pred_shares_key) ? load_word(a.pred_src.values, a.pred_src.dtype, row) : 0;
-            }
-#pragma unroll
-            for (int j = 0; j < NV; ++j)
-                vw[j][u] = (in && j < a.nv && a.val[j].values && !a.val_shares_key[j])
-                               ? static_cast<const uint64_t *>(a.val[j].values)[row]
-                               : 0;
-        }
-        // ---- compute phase
-#pragma unroll
-        for (int u = 0; u < AGG_U; ++u) {
-            int64_t row = base + int64_t(u) * blockDim.x + threadIdx.x;
-            bool pass = row < a.n;
-            if (PRED == 1 || PRED == 3) {
-                bool ok = pass && (PLAIN || row_valid(a.pred_src, row));
-                uint64_t w = a.pred_shares_key ? kw[u] : pw[u];
-                if (PRED == 1) pass = ok && cmp_lit(pred_op, pred_dt, w, pred_lit);
-                else pass = ok && eval_simple(a.pred, w, ok, flags) != 0;
-            } else if (PRED == 2) {
-                pass = pass && get_bit(static_cast<const uint8_t *>(a.pred_src.values), row) && row_valid(a.pred_src, row);
-            }
-            bool kok = pass && (PLAIN || row_valid(a.key_src, row));
-            uint64_t key;
-            if (KEY == 0) key = kw[u];
-            else if (KEY == 1) {
-                uint64_t x = kw[u];
-                bool neg = key_signed && (long long)x < 0;
-                uint64_t ur = (neg ? 0ull - x : x) & key_mask;
-                key = neg ? 0ull - ur : ur;
-            } else key = eval_simple(a.key, kw[u], kok, flags);
-            pass = kok;
-            if (!pass) continue;
-            if (!run_live || key != run_key) {
-                if (run_live) flush_run();
-                run_key = key;
-                run_live = true;
-            }
-#pragma unroll
-            for (int j = 0; j < NV; ++j) {
-                if (j >= a.nv) continue;
-                if (!PLAIN && !row_valid(a.val[j], row)) continue;
-                rcnt[j] += 1;
-                if (a.need_sum[j] || a.need_minmax[j]) {
-                    double x = word_as_f64(a.val_shares_key[j] ? kw[u] : vw[j][u], a.val[j].dtype);
-                    rsum[j] += x;
-                    if (x != x) rnan[j] = true;
-                    else {
-                        uint64_t xo = f64_to_ord(x);
-                        rmn[j] = xo < rmn[j] ? xo : rmn[j];
-                        rmx[j] = xo > rmx[j] ? xo : rmx[j];
-                    }
-                }
-            }
-        }
-    }
-    if (run_live) flush_run();
-    __syncthreads();
-    // ---- merge this workgroup's table into the global one
-    for (uint32_t s = threadIdx.x; s < slots; s += blockDim.x) {
-        uint64_t k = lkeys[s];
-        if (k == EMPTY_KEY) continue;
-        uint64_t key = (s == cap) ? EMPTY_KEY : k;
-        int64_t gslot = global_find_or_insert(g, key, flags);
-        if (gslot < 0) continue;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            if (j >= a.nv) continue;
-            uint32_t o = uint32_t(j) * slots + s;
-            uint32_t c = lcnt[o];
-            global_update(g, gslot, a.v0 + j, uint64_t(c & ~NAN_BIT), lsum[o], a.need_sum[j] != 0, lmn[o], lmx[o],
-                          a.need_minmax[j] != 0, (c & NAN_BIT) != 0);
-        }
-    }
-}
-
-using GroupedKernel = void (*)(AggArgs, GroupTable, int *);
-template <int PRED, int KEY> GroupedKernel pick_plain(bool plain) {
-    return plain ? agg_grouped_kernel<PRED, KEY, true> : agg_grouped_kernel<PRED, KEY, false>;
-}
-template <int PRED> GroupedKernel pick_key(int key, bool plain) {
-    switch (key) {
-    case 0: return pick_plain<PRED, 0>(plain);
-    case 1: return pick_plain<PRED, 1>(plain);
-    default: return pick_plain<PRED, 2>(plain);
-    }
-}
-GroupedKernel pick_grouped_kernel(int pred, int key, bool plain) {
-    switch (pred) {
-    case 0: return pick_key<0>(key, plain);
-    case 1: return pick_key<1>(key, plain);
-    case 2: return pick_key<2>(key, plain);
-    default: return pick_key<3>(key, plain);
-    }
-}
-
-// ------------------------------------------------------------------ un-grouped kernel
-struct Partial {
-    uint64_t cnt;
-    double sum;
-    double mn, mx;
-    uint32_t nan;
-    uint32_t pad;
-};
-
-__device__ __forceinline__ double shfl_down_f64(double v, int d) { return __shfl_down(v, d, 64); }
-
-__global__ void __launch_bounds__(AGG_BLOCK) agg_ungrouped_kernel(AggArgs a, Partial *partials, int *flags) {
-    uint64_t cnt[NV];
-    double sum[NV], mn[NV], mx[NV];
-    uint32_t nanf[NV];
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        cnt[j] = 0; sum[j] = 0.0; mn[j] = DBL_MAX; mx[j] = -DBL_MAX; nanf[j] = 0;
-    }
-    const int64_t step = int64_t(blockDim.x) * AGG_U;
-    for (int64_t base = int64_t(blockIdx.x) * step; base < a.n; base += int64_t(gridDim.x) * step) {
-        uint64_t pw[AGG_U], vw[NV][AGG_U];
-#pragma unroll
-        for (int u = 0; u < AGG_U; ++u) {
-            int64_t row = base + int64_t(u) * blockDim.x + threadIdx.x;
-            bool in = row < a.n;
-            pw[u] = (in && a.pred_mode == 1) ? load_word(a.pred_src.values, a.pred_src.dtype, row) : 0;
-#pragma unroll
-            for (int j = 0; j < NV; ++j)
-                vw[j][u] = (in && j < a.nv && a.val[j].values) ? static_cast<const uint64_t *>(a.val[j].values)[row] : 0;
-        }
-#pragma unroll
-        for (int u = 0; u < AGG_U; ++u) {
-            int64_t row = base + int64_t(u) * blockDim.x + threadIdx.x;
-            bool pass = row < a.n;
-            if (a.pred_mode == 1) {
-                bool ok = pass && row_valid(a.pred_src, row);
-                pass = ok && eval_simple(a.pred, pw[u], ok, flags) != 0;
-            } else if (a.pred_mode == 2) {
-                pass = pass && get_bit(static_cast<const uint8_t *>(a.pred_src.values), row) && row_valid(a.pred_src, row);
-            }
-            if (!pass) continue;
-#pragma unroll
-            for (int j = 0; j < NV; ++j) {
-                if (j >= a.nv || !row_valid(a.val[j], row)) continue;
-                cnt[j] += 1;
-                if (a.need_sum[j] || a.need_minmax[j]) {
-                    double x = word_as_f64(vw[j][u], a.val[j].dtype);
-                    sum[j] += x;
-                    if (x != x) nanf[j] = 1;
-                    else {
-                        mn[j] = x < mn[j] ? x : mn[j];
-                        mx[j] = x > mx[j] ? x : mx[j];
-                    }
-                }
-            }
-        }
-    }
-    __shared__ Partial wave_part[AGG_BLOCK / 64][NV];
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        for (int d = 32; d > 0; d >>= 1) {
-            cnt[j] += __shfl_down((unsigned long long)cnt[j], d, 64);
-            sum[j] += shfl_down_f64(sum[j], d);
-            double omn = shfl_down_f64(mn[j], d), omx = shfl_down_f64(mx[j], d);
-            mn[j] = omn < mn[j] ? omn : mn[j];
-            mx[j] = omx > mx[j] ? omx : mx[j];
-            nanf[j] |= __shfl_down(nanf[j], d, 64);
-        }
-        if (lane_id() == 0) {
-            Partial p{cnt[j], sum[j], mn[j], mx[j], nanf[j], 0};
-            wave_part[threadIdx.x / 64][j] = p;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < NV) {
-        int j = threadIdx.x;
-        Partial t{0, 0.0, DBL_MAX, -DBL_MAX, 0, 0};
-        for (int w = 0; w < int(blockDim.x) / 64; ++w) { // fixed order: deterministic
-            const Partial &p = wave_part[w][j];
-            t.cnt += p.cnt; t.sum += p.sum;
-            t.mn = p.mn < t.mn ? p.mn : t.mn;
-            t.mx = p.mx > t.mx ? p.mx : t.mx;
-            t.nan |= p.nan;
-        }
-        partials[size_t(blockIdx.x) * NV + j] = t;
-    }
-}
-
-// un-grouped fast path: plain 8-byte columns, optional integer range predicate on one column.
-// PRED: 0 none, 1 predicate column is value column 0 (one load serves both), 2 a separate column.
-template <int PRED, int NVT, bool VF64, bool VNULL>
-__global__ void __launch_bounds__(AGG_BLOCK) agg_ungrouped_fast_kernel(AggArgs a, FastPred fp, Partial *partials) {
-    uint64_t cnt[NVT];
-    double sum[NVT], mn[NVT], mx[NVT];
-    bool nanf[NVT];
-#pragma unroll
-    for (int j = 0; j < NVT; ++j) {
-        cnt[j] = 0; sum[j] = 0.0; mn[j] = DBL_MAX; mx[j] = -DBL_MAX; nanf[j] = false;
-    }
-    const uint64_t *__restrict__ predp = static_cast<const uint64_t *>(a.pred_src.values);
-    const uint64_t *__restrict__ valp[NVT];
-    const uint64_t *__restrict__ vvalid[NVT]; // VNULL: word-readable validity bitmaps, null = all valid
-    const uint64_t *__restrict__ pvalid = reinterpret_cast<const uint64_t *>(PRED != 0 ? a.pred_src.valid : nullptr);
-    int vdt[NVT];
-#pragma unroll
-    for (int j = 0; j < NVT; ++j) {
-        valp[j] = static_cast<const uint64_t *>(a.val[j].values);
-        vvalid[j] = reinterpret_cast<const uint64_t *>(a.val[j].valid);
-        vdt[j] = a.val[j].dtype;
-    }
-    const int64_t n = a.n, last = a.n - 1;
-    struct Tile {
-        uint64_t pw[AGG_U], vw[NVT][AGG_U];
-        uint64_t vv[VNULL ? NVT : 1][AGG_U], pv[VNULL ? AGG_U : 1];
-    };
-    auto load_tile = [&](Tile &t, int64_t base) {
-#pragma unroll
-        for (int u = 0; u < AGG_U; ++u) {
-            int64_t row = base + int64_t(u) * AGG_BLOCK + threadIdx.x;
-            row = row < last ? row : last;
-            if (PRED == 2) t.pw[u] = __builtin_nontemporal_load(&predp[row >> fp.row_shift]);
-#pragma unroll
-            for (int j = 0; j < NVT; ++j) t.vw[j][u] = __builtin_nontemporal_load(&valp[j][row]);
-            if (VNULL) {
-#pragma unroll
-                for (int j = 0; j < NVT; ++j) t.vv[j][u] = vvalid[j] ? vvalid[j][row >> 6] : ~0ull;
-                t.pv[u] = pvalid ? pvalid[row >> 6] : ~0ull;
-            }
-        }
-    };
-    auto process_tile = [&](const Tile &t, int64_t base) {
-#pragma unroll
-        for (int u = 0; u < AGG_U; ++u) {
-            int64_t row = base + int64_t(u) * AGG_BLOCK + threadIdx.x;
-            bool pass = row < n;
-            if (PRED != 0) pass = pass && range_pass(fp, PRED == 1 ? t.vw[0][u] : pred_extract(fp, t.pw[u], row));
-            if (VNULL) pass = pass && ((t.pv[u] >> (row & 63)) & 1ull); // a NULL predicate's row is all-NULL: contributes nothing
-            if (!pass) continue;
-#pragma unroll
-            for (int j = 0; j < NVT; ++j) {
-                double x = VF64 ? u2d(t.vw[j][u]) : word_as_f64(t.vw[j][u], vdt[j]);
-                if (VNULL && !((t.vv[j][u] >> (row & 63)) & 1ull)) continue; // NULL value: not counted (Q10)
-                cnt[j] += 1;
-                sum[j] += x;
-                nanf[j] = nanf[j] || (x != x);
-                mn[j] = fmin(mn[j], x);
-                mx[j] = fmax(mx[j], x);
-            }
-        }
-    };
-    const int64_t step = int64_t(AGG_BLOCK) * AGG_U;
-    const int64_t stride = int64_t(gridDim.x) * step;
-    int64_t base = int64_t(blockIdx.x) * step;
-    if (base < n) {
-        Tile A, B;
-        load_tile(A, base);
-        for (;;) {
-            load_tile(B, base + stride);
-            process_tile(A, base);
-            base += stride;
-            if (base >= n) break;
-            load_tile(A, base + stride);
-            process_tile(B, base);
-            base += stride;
-            if (base >= n) break;
-        }
-    }
-    __shared__ Partial wave_part[AGG_BLOCK / 64][NV];
-#pragma unroll
-    for (int j = 0; j < NVT; ++j) {
-        uint32_t nf = nanf[j] ? 1u : 0u;
-        for (int d = 32; d > 0; d >>= 1) {
-            cnt[j] += __shfl_down((unsigned long long)cnt[j], d, 64);
-            sum[j] += shfl_down_f64(sum[j], d);
-            double omn = shfl_down_f64(mn[j], d), omx = shfl_down_f64(mx[j], d);
-            mn[j] = omn < mn[j] ? omn : mn[j];
-            mx[j] = omx > mx[j] ? omx : mx[j];
-            nf |= __shfl_down(nf, d, 64);
-        }
-        if (lane_id() == 0) {
-            Partial p{cnt[j], sum[j], mn[j], mx[j], nf, 0};
-            wave_part[threadIdx.x / 64][j] = p;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < NVT) {
-        int j = threadIdx.x;
-        Partial t{0, 0.0, DBL_MAX, -DBL_MAX, 0, 0};
-        for (int w = 0; w < AGG_BLOCK / 64; ++w) {
-            const Partial &p = wave_part[w][j];
-            t.cnt += p.cnt; t.sum += p.sum;
-            t.mn = p.mn < t.mn ? p.mn : t.mn;
-            t.mx = p.mx > t.mx ? p.mx : t.mx;
-            t.nan |= p.nan;
-        }
-        partials[size_t(blockIdx.x) * NV + j] = t;
-    }
-}
-
-using UngroupedFastKernel = void (*)(AggArgs, FastPred, Partial *);
-template <int PRED, bool VNULL> UngroupedFastKernel pick_ungrouped_fast_nv(int nv, bool vf64) {
-    if (nv == 1) return vf64 ? agg_ungrouped_fast_kernel<PRED, 1, true, VNULL> : agg_ungrouped_fast_kernel<PRED, 1, false, VNULL>;
-    return vf64 ? agg_ungrouped_fast_kernel<PRED, 2, true, VNULL> : agg_ungrouped_fast_kernel<PRED, 2, false, VNULL>;
-}
-template <bool VNULL> UngroupedFastKernel pick_ungrouped_fast_pred(int pred, int nv, bool vf64) {
-    return pred == 0 ? pick_ungrouped_fast_nv<0, VNULL>(nv, vf64) : pred == 1 ? pick_ungrouped_fast_nv<1, VNULL>(nv, vf64) : pick_ungrouped_fast_nv<2, VNULL>(nv, vf64);
-}
-UngroupedFastKernel pick_ungrouped_fast(int pred, int nv, bool vf64, bool vnull) {
-    return vnull ? pick_ungrouped_fast_pred<true>(pred, nv, vf64) : pick_ungrouped_fast_pred<false>(pred, nv, vf64);
-}
-
-__global__ void agg_ungrouped_fold_kernel(const Partial *partials, int nblocks, int nv, int v0, GroupTable g) {
-    int j = threadIdx.x;
-    if (j >= nv) return;
-    Partial t{0, 0.0, DBL_MAX, -DBL_MAX, 0, 0};
-    for (int b = 0; b < nblocks; ++b) {
-        const Partial &p = partials[size_t(b) * NV + j];
-        t.cnt += p.cnt; t.sum += p.sum;
-        t.mn = p.mn < t.mn ? p.mn : t.mn;
-        t.mx = p.mx > t.mx ? p.mx : t.mx;
-        t.nan |= p.nan;
-    }
-    size_t o = size_t(v0 + j) * (size_t(g.cap) + 1);
-    g.cnt[o] += t.cnt;
-    g.sum[o] += t.sum;
-    uint64_t omn = f64_to_ord(t.mn), omx = f64_to_ord(t.mx);
-    if (omn < g.mn[o]) g.mn[o] = omn;
-    if (omx > g.mx[o]) g.mx[o] = omx;
-    g.nan[o] |= t.nan;
-}
+#include "aggregate_kernels.hpp"
 
 // ------------------------------------------------------------------ host side
 struct TableBufs {
@@ -738,21 +297,25 @@ constexpr uint64_t DIRECT_WIDE_SLOTS = 5840;
 // … and when no aggregate asks for min / max (count / sum / avg: the MM = false instance, 12 bytes per slot): 13633 slots in 160 KB
 constexpr uint64_t DIRECT_WIDE_SLOTS_NOMM = 13632;
 constexpr uint64_t RANGE_TIER_MAX_SLOTS = 5120;             // slots of one LDS table of the range tier (28 bytes each)
-constexpr uint64_t TINY_SALT = 0xC2B2AE3D27D4EB4Full;       // nqe_ctx::agg_key_ranges[hint ^ salt] present: the tiny-groups kernel met a key outside [0, m)
-constexpr uint64_t PART_RANGE_SALT = 0x9E3779B97F4A7C15ull; // nqe_ctx::agg_key_ranges[hint ^ salt]: the key range of the query's groups (range partitions)
+// (What the A/B runs of rounds 2-6 settled sits next to what it sizes: FLAG_CHECK_MASK, SUBSETS_MAX_LOG2, SOA_THREADS, SLAB_PARTS_FIRST_LOG2 and
+// RANGE_SLOTS_LOG2 in aggregate_common.hpp, RANGE_EMIT_WIDE_SPAN in aggregate_tail.hpp; DESIGN.md §9 "retired switches".)
 
 // ---- PhysicalAggregatePlan::execute (aggregate/mod.rs:113-222) on the device, one object per execution:
-//   plan      prepare (key expression, predicate) -> size_tables -> load_hints (what this query shape did last time) -> sample_keys (the
-//             first execution's key sample picks the starting tier) -> pick_key_range (a plain key column addressed by key - min);
-//   execute   run: per attempt begin_attempt (the group table), then per pass of 1-3 value columns launch_pass = shape_pass (which
-//             kernel variant the pass's columns, key and predicate admit) + ONE tier: tier_slab (partitioned, fixed-capacity slabs),
-//             tier_exact (partitioned, exact sizes / two levels), tier_streaming (the single-pass LDS-table kernels and the run-time
-//             specialised one), the general hashed kernel, or pass_ungrouped;
-//   react     finish_attempt: the tail ahead of ONE flag read-back, then react_to_flags — an overflowed tier names the next one, the
-//             attempt is redone there and the plan hint remembers it — or the result.
-// Switches: the A/B diagnostics are read ONCE per context (nqe_ctx::agg_sw, AggSwitches in nqe_internal.hpp; listed in DESIGN.md §9);
-// the ones tests flip between calls are read per call where they are used (NQE_NO_PLAN_HINTS, NQE_NO_KEY_SAMPLE, NQE_NO_RANGE_PARTITION,
-// NQE_NO_RANGE_TAIL, NQE_NO_AGG_JIT, NQE_TEST_SLAB_OOM).
+//   plan      prepare (key expression; plan_predicate: the predicate's form) -> size_tables -> load_hints (hash_query_shape: the memo's key;
+//             recall_memo: what this query shape did last time) -> sample_keys (the first execution's key sample picks the starting tier:
+//             wants_key_sample, start_from_sample) -> pick_key_range (a plain key column addressed by key - min);
+//   execute   run: per attempt begin_attempt (the group table), then per pass of 1-3 value columns launch_pass = shape_pass (which kernel
+//             variant the pass's columns, key and predicate admit: classify_key, resolve_list_pred / resolve_tree_pred, pick_pred_variant,
+//             classify_chain_pred) + ONE tier: tier_slab (partitioned, fixed-capacity slabs; range_tail + range_emit behind key-range
+//             partitions), tier_exact (partitioned, exact sizes / two levels), tier_streaming (shape_direct_table, then the first that takes
+//             the pass of try_register_kernel, try_specialised_kernel, launch_fast_kernel + fold_direct_partials), the general hashed
+//             kernel, or pass_ungrouped;
+//   react     finish_attempt: the tail ahead of ONE flag read-back, then react_to_flags — react_to_key_faults, react_partitioned or
+//             react_streaming, react_table_full: an overflowed tier names the next one, the attempt is redone there (redo) and the memo
+//             (aggregate_memo.hpp, nqe_ctx::agg_memo) remembers it — or the result.
+// Switches: NQE_DEBUG and the test hook NQE_TINY_UNPACK_TILES are read ONCE per context (nqe_ctx::agg_sw); the ones tests flip
+// between calls are read per call where they are used (NQE_NO_PLAN_HINTS, NQE_NO_KEY_SAMPLE, NQE_NO_RANGE_PARTITION, NQE_NO_RANGE_TAIL,
+// NQE_NO_AGG_JIT, NQE_NO_WIDE_DIRECT, NQE_TEST_SLAB_OOM).
 AggResult run_aggregate(nqe_ctx *ctx, const nqe_table *in, const nqe_expr_node *pred, int pred_nodes, const nqe_expr_node *group, int group_nodes,
                         const nqe_aggregate *aggs, int naggs, bool partial);
 
@@ -800,7 +363,11 @@ struct AggRun {
     int subsets_log2 = 0, slab_parts_log2 = 8;
     uint64_t hint_key = 0;
     bool any_val_nullable = false, subsets_ok = false, plain_int_key = false, no_hints_env = false, range_sampled = false;
-    uint64_t range_limit = 4096, key_flip = 0;
+    uint64_t range_limit = 4096;
+    // the sort-order flip of the keys.  (From the key SOURCE's type, which is the key's own: arithmetic keeps its operands' type (expr.hip: parse),
+    // a Utf8 key's codes are Int64, an evaluated key column has the expression's type — so it serves wherever kinfo.out_dtype was asked.  Not in
+    // emit() / emit_ranked(): the merges call those too, with the key type of the tables they were handed.)
+    uint64_t key_flip = 0;
     uint64_t direct_pair_limit = 8192; // values of a key range the direct-mapped tables of TWO key subsets take (AggArgs::direct_sub_width)
     uint64_t direct_one_limit = 4096; // values of a key range ONE direct-mapped workgroup table takes (DIRECT_WIDE_SLOTS where the table has no key words)
     // ---- the attempt
@@ -818,6 +385,10 @@ struct AggRun {
     int blocks_per_cu = 1, grid = 1, kk = 2, fast_key = -1, pk = 0, fp = 0;
     AggArgs ka;
     FastPred fpred;
+    // ---- the streaming tier's launch shape (tier_streaming: shape_direct_table)
+    int fgrid = 1;
+    size_t fshmem = 0;
+    bool nomm = false, share = false;
 
     AggRun(nqe_ctx *c, const nqe_table *t, const nqe_expr_node *p, int pn, const nqe_expr_node *g, int gn, const nqe_aggregate *ag, int na, bool part)
         : ctx(c), in(t), pred(p), pred_nodes(pn), group(g), group_nodes(gn), aggs(ag), naggs(na), partial(part), sw(c->agg_sw) {}
@@ -827,28 +398,121 @@ struct AggRun {
         a.pred_mode = 2;
         a.pred_src = src_of(pred_col);
     }
-    std::pair<int64_t, uint64_t> measure_key_range();
+    // ---- plan
     bool prepare();
+    void plan_predicate();
     void size_tables();
+    void hash_query_shape();
+    void recall_memo();
     void load_hints();
+    std::pair<int64_t, uint64_t> measure_key_range();
+    bool simple_mod_key() const;
+    bool wants_key_sample() const;
     void sample_keys();
+    void start_from_sample(uint64_t D, double G, uint64_t ordmin, uint64_t ordmax);
+    void part_range_from_sample(uint64_t ordmin, uint64_t ordmax);
     void pick_key_range();
+    // ---- execute
     void begin_attempt();
     PassStatus launch_pass(int v0);
     PassStatus shape_pass();
+    void classify_key();
+    int pred_word_of(const DevColumn &c, const void *&other, bool &ok);
+    void resolve_list_pred();
+    void resolve_tree_pred();
+    void pick_pred_variant();
+    void classify_chain_pred();
     PassStatus tier_slab();
+    int slab_partitions_log2(bool range_part, bool range_tier) const;
     void range_tail(const AggArgs &sa, const SlabArgs &sl, uint32_t rslots);
     void range_emit(int parts_log2, int Q, uint32_t rslots, uint64_t span, int64_t key_min);
     void tier_exact();
     PassStatus tier_streaming(int v0);
+    void shape_direct_table();
+    bool try_register_kernel();
+    bool try_specialised_kernel(int v0);
+    void launch_fast_kernel();
+    void fold_direct_partials(const BufRef &partials, uint32_t pspan, size_t pcol_words);
     void pass_ungrouped(int v0);
+    // ---- react
     bool finish_attempt(AggResult *out);
+    bool remember_group_range(uint64_t ordlo, uint64_t ordhi);
     void keys_to_strings(AggResult &res);
+    bool react_to_flags(const int *f);
+    bool react_to_key_faults(const int *f);
+    bool react_partitioned(const int *f);
+    bool react_streaming(const int *f);
+    bool measured_range_picks_the_tier(bool *to_subsets);
+    bool react_table_full(const int *f);
+
+    // ---- steps the tier ladder repeats
+    // what this context remembers of the query shape (aggregate_memo.hpp); entry(): a new shape arriving at a full table clears it first
+    AggMemo &memo() { return ctx->agg_memo.entry(hint_key); }
+    AggStart slab_start() const { return slab_parts_log2 < PARTS_LOG2 ? AggStart::SlabFirstParts : AggStart::SlabAllParts; }
+    bool redo() { // the attempt again (the members say where)
+        flags_reset(ctx);
+        return true;
+    }
+    void go_partitioned() {
+        subsets_log2 = 0;
+        partition_mode = true;
+        cap = std::max(cap, sized_cap);
+    }
+    void grow_cap_for_subsets(int k) { cap = std::max(cap, std::min(sized_cap, RANK_MAX_CAP << k)); } // room in the group table for 2^k workgroup tables' worth of groups
+    void adopt_key_range(int64_t min, uint64_t span) { // the streaming tier addresses its tables by key - min
+        range_on = true;
+        range_min = min;
+        range_span = span;
+    }
+    // one value column: a 4096-slot workgroup table (147 KB, one workgroup per CU) doubles the distinct keys a table may hold
+    static void one_column_table(AggArgs &args, size_t &shmem, int *blocks = nullptr) {
+        args.lds_cap = 4096;
+        args.lds_shift = 64 - 12;
+        shmem = ((size_t(4097) * (8 + 28)) + 15) / 16 * 16;
+        if (blocks) *blocks = 1;
+    }
     // values of a measured key range the streaming tier addresses directly: one table's (direct_one_limit), or 2^subsets_log2 tables of range_limit
     uint64_t one_table_or_subsets_limit() const { return subsets_log2 == 1 ? direct_pair_limit : (subsets_log2 ? (range_limit << subsets_log2) : direct_one_limit); }
-    bool react_to_flags(const int *f, const Collected &pre);
     AggResult run();
 };
+
+// the predicate's form: a simple chain (pred_mode 1), a list of range tests (3) or a fault-free tree (4) the streaming kernel evaluates
+// itself — both resolved per pass, see shape_pass —, the run-time specialised kernel (jit_whole), or a materialised Boolean column (2)
+void AggRun::plan_predicate() {
+    ExprInfo pinfo = analyze_expr(in, pred, pred_nodes);
+    pred_may_fault = pinfo.may_fault;
+    if (pinfo.out_dtype != NQE_BOOLEAN)
+        fail(NQE_ERR_NOT_SUPPORTED, "predicate is not a BooleanArray (selection.rs:61 unwrap panics)");
+    if (pinfo.simple) {
+        a.pred_mode = 1;
+        a.pred = pinfo.s;
+        a.pred_src = src_of(in->cols[size_t(pinfo.s.col)]);
+    } else if (grouped && match_conj(in, pred, pred_nodes, &a.conj, conj_col)) {
+        a.pred_mode = 3; // resolved (or materialised) per pass, see the launch section
+    } else if (grouped && !pinfo.may_fault && match_tree_pred(in, pred, pred_nodes, &tree)) {
+        a.pred_mode = 4; // likewise
+    } else {
+        // A tree the static kernels can only take as a materialised Boolean column (column-with-column compares, products of
+        // columns, ...): one more pass over its columns plus the bitmap.  When the query has the shape of the lean specialised
+        // streaming kernel (expr_jit.hpp: nqe_jit_agg — key `col % m` with 512-4096 table slots, value columns without NULLs)
+        // and that kernel is compiled, the predicate is evaluated there, in the aggregation pass: the rest of this function then
+        // sees a query without a predicate, and every pass is launched through the specialised kernel (jit_whole).
+        const int klast = kinfo.s.nops - 1;
+        bool cand = grouped && !utf8_key && kinfo.simple && !kinfo.may_fault && !pinfo.may_fault && klast >= 0 && kinfo.s.op[klast] == NQE_OP_MODULOS && !kinfo.s.lit_left[klast] &&
+                    (kinfo.s.op_dtype[klast] == NQE_INT64 || kinfo.s.op_dtype[klast] == NQE_UINT64) && !in->cols[size_t(kinfo.s.col)].validity && !plan.val_cols.empty() &&
+                    plan.val_cols.size() <= 2 && !getenv("NQE_NO_AGG_JIT");
+        for (int c : plan.val_cols) cand = cand && is_word_type(in->cols[size_t(c)].dtype) && !in->cols[size_t(c)].validity;
+        if (cand) {
+            for (int c : plan.val_cols) {
+                uint32_t sp;
+                int64_t bi;
+                cand = cand && aggregate_tree_specialised(ctx, in, pred, pred_nodes, group, group_nodes, c, 1, nullptr, &sp, &bi, true);
+            }
+        }
+        if (cand) jit_whole = true; // (a.pred_mode stays 0)
+        else materialize_pred();
+    }
+}
 
 // key expression (group_expr[0] only, quirk Q8) and predicate.  true: `early` holds the result (a general key expression under a filter)
 bool AggRun::prepare() {
@@ -885,42 +549,7 @@ bool AggRun::prepare() {
             return true;
         }
     }
-    // ---- predicate
-    if (has_pred) {
-        ExprInfo pinfo = analyze_expr(in, pred, pred_nodes);
-        pred_may_fault = pinfo.may_fault;
-        if (pinfo.out_dtype != NQE_BOOLEAN)
-            fail(NQE_ERR_NOT_SUPPORTED, "predicate is not a BooleanArray (selection.rs:61 unwrap panics)");
-        if (pinfo.simple) {
-            a.pred_mode = 1;
-            a.pred = pinfo.s;
-            a.pred_src = src_of(in->cols[size_t(pinfo.s.col)]);
-        } else if (grouped && match_conj(in, pred, pred_nodes, &a.conj, conj_col)) {
-            a.pred_mode = 3; // resolved (or materialised) per pass, see the launch section
-        } else if (grouped && !pinfo.may_fault && match_tree_pred(in, pred, pred_nodes, &tree)) {
-            a.pred_mode = 4; // likewise
-        } else {
-            // A tree the static kernels can only take as a materialised Boolean column (column-with-column compares, products of
-            // columns, ...): one more pass over its columns plus the bitmap.  When the query has the shape of the lean specialised
-            // streaming kernel (expr_jit.hpp: nqe_jit_agg — key `col % m` with 512-4096 table slots, value columns without NULLs)
-            // and that kernel is compiled, the predicate is evaluated there, in the aggregation pass: the rest of this function then
-            // sees a query without a predicate, and every pass is launched through the specialised kernel (jit_whole).
-            const int klast = kinfo.s.nops - 1;
-            bool cand = grouped && !utf8_key && kinfo.simple && !kinfo.may_fault && !pinfo.may_fault && klast >= 0 && kinfo.s.op[klast] == NQE_OP_MODULOS && !kinfo.s.lit_left[klast] &&
-                        (kinfo.s.op_dtype[klast] == NQE_INT64 || kinfo.s.op_dtype[klast] == NQE_UINT64) && !in->cols[size_t(kinfo.s.col)].validity && !plan.val_cols.empty() &&
-                        plan.val_cols.size() <= 2 && !getenv("NQE_NO_AGG_JIT");
-            for (int c : plan.val_cols) cand = cand && is_word_type(in->cols[size_t(c)].dtype) && !in->cols[size_t(c)].validity;
-            if (cand) {
-                for (int c : plan.val_cols) {
-                    uint32_t sp;
-                    int64_t bi;
-                    cand = cand && aggregate_tree_specialised(ctx, in, pred, pred_nodes, group, group_nodes, c, 1, nullptr, &sp, &bi, true);
-                }
-            }
-            if (cand) jit_whole = true; // (a.pred_mode stays 0)
-            else materialize_pred();
-        }
-    }
+    if (has_pred) plan_predicate();
     if (grouped) {
         a.has_key = 1;
         if (utf8_key) {
@@ -970,89 +599,91 @@ void AggRun::size_tables() {
         cap = std::min(sized_cap, RANK_MAX_CAP);
     }
     // KEY-RANGE partitions of the slab form (aggregate_common.hpp: SlabArgs::range_span): the range they work from — the exact one an
-    // earlier execution's dense tail measured (remembered under a salted hint key), or this execution's key sample (`col % m`: what the
+    // earlier execution's tail measured (AggMemo::part_range), or this execution's key sample (`col % m`: what the
     // modulus allows; a plain column: the sample's range padded by 1/256).  span 0: none; a key outside it sends the attempt back to hashed
-    // partitions (a sampled range is then replaced by the measured one, a remembered one by (0, 0): never again).
+    // partitions (a sampled range is then replaced by the measured one, a remembered one by "never again").
     // NQE_NO_RANGE_PARTITION=1: hashed partitions only (A/B)
     range_part_ok = getenv("NQE_NO_RANGE_PARTITION") == nullptr; // (read per call: tests switch it)
-    three_on = !sw.no_three_column_pass;
-    // a plain integer key column whose value RANGE fits a workgroup table (nqe_ctx::agg_key_ranges)
+    three_on = true;
     // Between one LDS table's worth of groups and the partitioned path: the fast kernel with two key subsets (see
     // AggArgs::subsets_log2) — every row is read by two workgroups, each of which keeps its half of the keys.  Rows of the other
     // half cost a wave as many issue slots as its own (lanes are masked, instructions are not skipped), so the kernel time doubles:
     // per 10^8 rows 0.80-0.91 ms at 4096-6000 groups against 1.29 ms partitioned; with four subsets (1.5-1.7 ms) partitioning wins.
     // slab form of the partitioned path: 256 partitions first, PARTS when one of them holds more distinct keys than a workgroup table
-    slab_parts_log2 = std::min(std::max(sw.slab_parts_first, 6), PARTS_LOG2);
+    slab_parts_log2 = SLAB_PARTS_FIRST_LOG2;
+}
+
+// the memo's key (nqe_ctx::agg_memo): FNV-1a over everything that decides which kernels the query takes — the key column's buffer and
+// expression, the predicate and its column, the value columns (buffers, validity, types) and the row count — so that what is remembered
+// is only ever applied to the very query shape that recorded it.  0: nothing is remembered for this query
+void AggRun::hash_query_shape() {
+    hint_key = 0;
+    if (!(grouped && a.key_src.values && in->rows >= (int64_t(1) << 18))) return;
+    hint_key = 1469598103934665603ull;
+    auto mix = [&](const void *p, size_t nbytes) {
+        const unsigned char *b = static_cast<const unsigned char *>(p);
+        for (size_t i = 0; i < nbytes; ++i) hint_key = (hint_key ^ b[i]) * 1099511628211ull;
+    };
+    const void *kp = a.key_src.values;
+    mix(&in->uid, sizeof(in->uid)); // (the table handle's identity: nqe_internal.hpp)
+    mix(&kp, sizeof(kp));
+    mix(&in->rows, sizeof(in->rows));
+    mix(&a.key, sizeof(a.key));
+    mix(&a.key_src, sizeof(a.key_src));
+    mix(&a.pred_mode, sizeof(a.pred_mode));
+    if (a.pred_mode == 3) {
+        mix(&a.conj, sizeof(a.conj));
+        mix(conj_col, sizeof(conj_col));
+    } else if (a.pred_mode == 4) {
+        mix(&tree, sizeof(tree));
+    } else if (a.pred_mode) {
+        mix(&a.pred, sizeof(a.pred));
+        mix(&a.pred_src, sizeof(a.pred_src));
+    }
+    if (jit_whole) // the predicate lives in the specialised kernel only (pred_mode 0): its nodes tell this shape from the unfiltered query
+        for (int i = 0; i < pred_nodes; ++i) {
+            mix(&pred[i], offsetof(nqe_expr_node, value));
+            if (!(pred[i].kind == NQE_EXPR_LITERAL && pred[i].dtype == NQE_UTF8)) mix(&pred[i].value, sizeof(pred[i].value));
+        }
+    for (int c : plan.val_cols) {
+        const DevColumn &dc = in->cols[size_t(c)];
+        const void *vp = dc.values ? dc.values->ptr : nullptr, *vv = dc.valid();
+        mix(&vp, sizeof(vp));
+        mix(&vv, sizeof(vv));
+        mix(&dc.dtype, sizeof(dc.dtype));
+    }
+    if (hint_key == 0) hint_key = 1;
+}
+
+// where the query shape's earlier executions ended (NQE_NO_PLAN_HINTS: nothing is recalled; everything is still recorded)
+void AggRun::recall_memo() {
+    const bool no_hints = getenv("NQE_NO_PLAN_HINTS") != nullptr; // diagnostics (A/B runs; read per call: tests switch it)
+    const AggMemo *m = (hint_key && !no_hints) ? ctx->agg_memo.find(hint_key) : nullptr;
+    if (!m) return;
+    if (m->part_range == AggMemo::PartRange::Never) range_part_ok = false;
+    else if (m->part_range == AggMemo::PartRange::Known) {
+        part_min = m->part_min;
+        part_span = m->part_span;
+    }
+    if (m->tiny_rejected) tiny_ok = false; // a key outside [0, m) was met before
+    if (m->start == AggStart::Unknown) return;
+    if (m->key32_failed) key32_failed = true;      // keys beyond int32: 16-byte tuples
+    if (m->no_three_column_pass) three_on = false; // more groups than the three-column instance holds
+    switch (m->start) {
+    case AggStart::SlabAllParts: slab_parts_log2 = PARTS_LOG2; go_partitioned(); break;
+    case AggStart::ExactForm: slab_failed = true; go_partitioned(); break; // a slab overflowed or did not fit
+    case AggStart::SlabFirstParts: go_partitioned(); break;                // the smaller first count was enough
+    case AggStart::TwoSubsets:
+        subsets_log2 = 1;
+        grow_cap_for_subsets(subsets_log2);
+        break;
+    default: break; // Streaming: where every execution starts
+    }
 }
 
 void AggRun::load_hints() {
-    // plan hint (see nqe_ctx::agg_hints): FNV-1a over everything that decides which kernels the query takes — the key column's
-    // buffer and expression, the predicate and its column, the value columns (buffers, validity, types) and the row count — so
-    // that a hint is only ever applied to the very query shape that recorded it
-    hint_key = 0;
-    if (grouped && a.key_src.values && in->rows >= (int64_t(1) << 18)) {
-        hint_key = 1469598103934665603ull;
-        auto mix = [&](const void *p, size_t nbytes) {
-            const unsigned char *b = static_cast<const unsigned char *>(p);
-            for (size_t i = 0; i < nbytes; ++i) hint_key = (hint_key ^ b[i]) * 1099511628211ull;
-        };
-        const void *kp = a.key_src.values;
-        mix(&in->uid, sizeof(in->uid)); // (the table handle's identity: nqe_internal.hpp)
-        mix(&kp, sizeof(kp));
-        mix(&in->rows, sizeof(in->rows));
-        mix(&a.key, sizeof(a.key));
-        mix(&a.key_src, sizeof(a.key_src));
-        mix(&a.pred_mode, sizeof(a.pred_mode));
-        if (a.pred_mode == 3) {
-            mix(&a.conj, sizeof(a.conj));
-            mix(conj_col, sizeof(conj_col));
-        } else if (a.pred_mode == 4) {
-            mix(&tree, sizeof(tree));
-        } else if (a.pred_mode) {
-            mix(&a.pred, sizeof(a.pred));
-            mix(&a.pred_src, sizeof(a.pred_src));
-        }
-        if (jit_whole) // the predicate lives in the specialised kernel only (pred_mode 0): its nodes tell this shape from the unfiltered query
-            for (int i = 0; i < pred_nodes; ++i) {
-                mix(&pred[i], offsetof(nqe_expr_node, value));
-                if (!(pred[i].kind == NQE_EXPR_LITERAL && pred[i].dtype == NQE_UTF8)) mix(&pred[i].value, sizeof(pred[i].value));
-            }
-        for (int c : plan.val_cols) {
-            const DevColumn &dc = in->cols[size_t(c)];
-            const void *vp = dc.values ? dc.values->ptr : nullptr, *vv = dc.valid();
-            mix(&vp, sizeof(vp));
-            mix(&vv, sizeof(vv));
-            mix(&dc.dtype, sizeof(dc.dtype));
-        }
-        if (hint_key == 0) hint_key = 1;
-        const bool no_hints = getenv("NQE_NO_PLAN_HINTS") != nullptr; // diagnostics (A/B runs; read per call: tests switch it)
-        if (!no_hints) {
-            auto pr = ctx->agg_key_ranges.find(hint_key ^ PART_RANGE_SALT);
-            if (pr != ctx->agg_key_ranges.end()) {
-                if (pr->second.second == 0) range_part_ok = false;
-                else {
-                    part_min = pr->second.first;
-                    part_span = pr->second.second;
-                }
-            }
-        }
-        if (!no_hints && ctx->agg_key_ranges.find(hint_key ^ TINY_SALT) != ctx->agg_key_ranges.end()) tiny_ok = false; // a key outside [0, m) was met before
-        auto it = ctx->agg_hints.find(hint_key);
-        if (!no_hints && it != ctx->agg_hints.end()) {
-            const uint8_t hv = it->second & 0x3f;
-            if (it->second & 0x40) key32_failed = true; // keys beyond int32: 16-byte tuples
-            if (it->second & 0x80) three_on = false;    // more groups than the three-column instance holds
-            if (hv == 1 || hv == 16 || hv == 17) { // 1: PARTS partitions, 16: the smaller first count was enough
-                partition_mode = true;             // 17: the exact form (a slab overflowed or did not fit)
-                if (hv == 1) slab_parts_log2 = PARTS_LOG2;
-                if (hv == 17) slab_failed = true;
-                cap = std::max(cap, sized_cap);
-            } else if (hv >= 2 && hv - 1 <= sw.subsets_max) {
-                subsets_log2 = hv - 1;
-                cap = std::max(cap, std::min(sized_cap, RANK_MAX_CAP << subsets_log2));
-            }
-        }
-    }
+    hash_query_shape();
+    recall_memo();
     any_val_nullable = false;
     for (int c : plan.val_cols) any_val_nullable = any_val_nullable || in->cols[size_t(c)].validity != nullptr;
     // the two-subset instances exist for one value column and sources without validity bitmaps
@@ -1080,125 +711,138 @@ std::pair<int64_t, uint64_t> AggRun::measure_key_range() {
     // (span 0: the whole 64-bit range, or no rows)
     return std::make_pair(int64_t(h[0] ^ key_flip), h[1] >= h[0] ? h[1] - h[0] + 1 : 0ull);
 }
-void AggRun::sample_keys() {
-    // ---- the first execution of a query shape (nothing remembered, or NQE_NO_PLAN_HINTS): a SAMPLE of the keys picks the starting
-    // tier instead of falling through abandoned ones — the reference's run_sql is one-shot (db.rs:24-37), so the first execution is
-    // the one that counts.  65536 keys (key_sample_kernel, ~20 us): their distinct count is a lower bound of the groups, so a tier it
-    // rules out would certainly have overflowed; their min / max stand in for the full pass over a plain key column (the streaming
-    // kernel checks every key against the range, and a key outside it asks for the exact measurement).  Only without a predicate: a
-    // filter may leave far fewer groups than the table holds.
-    no_hints_env = getenv("NQE_NO_PLAN_HINTS") != nullptr; // (both read per call: tests switch them)
-    const bool no_sample = getenv("NQE_NO_KEY_SAMPLE") != nullptr;
-    const bool simple_mod_key = a.key.nops == 1 && a.key.op[0] == NQE_OP_MODULOS && !a.key.lit_left[0] && (a.key.op_dtype[0] == NQE_INT64 || a.key.op_dtype[0] == NQE_UINT64) &&
-                                a.key.aux[0].abs_lit > 1;
+// `col % m`, m > 1, over an integer column
+bool AggRun::simple_mod_key() const {
+    return a.key.nops == 1 && a.key.op[0] == NQE_OP_MODULOS && !a.key.lit_left[0] && (a.key.op_dtype[0] == NQE_INT64 || a.key.op_dtype[0] == NQE_UINT64) && a.key.aux[0].abs_lit > 1;
+}
+
+// is this the first execution of a query shape the key sample can say something about?
+bool AggRun::wants_key_sample() const {
+    const bool no_sample = getenv("NQE_NO_KEY_SAMPLE") != nullptr; // (read per call: tests switch it)
     // (the tiers the sample may start in exist for the streaming kernel's shapes only: at least one value column, every one of them
     // 8-byte words — `select k from t group by k` and count() over a Utf8 / Boolean column go through the general kernel, which takes
     // neither key subsets nor a densely written table)
     bool sample_shape = V >= 1;
     for (int c : plan.val_cols) sample_shape = sample_shape && is_word_type(in->cols[size_t(c)].dtype) && in->cols[size_t(c)].values;
-    if (grouped && hint_key && !no_sample && sample_shape && in->rows >= KEY_SAMPLE_MIN_ROWS && a.pred_mode == 0 && !jit_whole && a.key_src.values && !a.key_src.valid && !utf8_key &&
-        (a.key_src.dtype == NQE_INT64 || a.key_src.dtype == NQE_UINT64) &&
-        (a.key.nops == 0 || (simple_mod_key && (key_flip ? 2 * a.key.aux[0].abs_lit - 1 : a.key.aux[0].abs_lit) > direct_one_limit && a.key.aux[0].abs_lit > range_limit)) && // (`col % m`, its keys within a workgroup table: nothing to find out)
-        (no_hints_env || (ctx->agg_hints.find(hint_key) == ctx->agg_hints.end() && ctx->agg_key_ranges.find(hint_key) == ctx->agg_key_ranges.end()))) {
-        BufRef set = dev_alloc(ctx, (size_t(1) << KEY_SAMPLE_SLOTS_LOG2) * 8), so = dev_alloc(ctx, 32);
-        NQE_HIP_CHECK(hipMemsetAsync(set->ptr, 0xFF, (size_t(1) << KEY_SAMPLE_SLOTS_LOG2) * 8, ctx->stream));
-        NQE_HIP_CHECK(hipMemsetAsync(so->ptr, 0xFF, 8, ctx->stream));
-        NQE_HIP_CHECK(hipMemsetAsync(static_cast<char *>(so->ptr) + 8, 0, 24, ctx->stream));
-        launch(ctx, "agg_key_sample", key_sample_kernel, dim3(KEY_SAMPLE / 256), dim3(256), 0, (const uint64_t *)a.key_src.values, in->rows, a.key, key_flip,
-               (unsigned long long *)set->ptr, (unsigned long long *)so->ptr);
-        uint64_t h[4];
-        NQE_HIP_CHECK(hipMemcpyAsync(h, so->ptr, 32, hipMemcpyDeviceToHost, ctx->stream));
-        sync(ctx);
-        const uint64_t D = h[2] + (h[3] ? 1 : 0);
-        // groups of the whole table from the sample's distinct count: D = G (1 - exp(-S / G)) (uniform keys; skew only lowers it)
-        double G = double(D);
-        if (D > uint64_t(KEY_SAMPLE) / 2) {
-            double lo = double(D), hi = 1e13;
-            for (int it = 0; it < 60; ++it) {
-                const double mid = std::sqrt(lo * hi);
-                (mid * (1.0 - std::exp(-double(KEY_SAMPLE) / mid)) < double(D) ? lo : hi) = mid;
-            }
-            G = lo;
+    // Only without a predicate: a filter may leave far fewer groups than the table holds
+    if (!(grouped && hint_key && !no_sample && sample_shape && in->rows >= KEY_SAMPLE_MIN_ROWS && a.pred_mode == 0 && !jit_whole && a.key_src.values && !a.key_src.valid && !utf8_key &&
+          (a.key_src.dtype == NQE_INT64 || a.key_src.dtype == NQE_UINT64)))
+        return false;
+    // (`col % m`, its keys within a workgroup table: nothing to find out)
+    const uint64_t m = a.key.aux[0].abs_lit;
+    if (!(a.key.nops == 0 || (simple_mod_key() && (key_flip ? 2 * m - 1 : m) > direct_one_limit && m > range_limit))) return false;
+    if (no_hints_env) return true;
+    const AggMemo *known = ctx->agg_memo.find(hint_key);
+    return !known || known->first_execution();
+}
+
+void AggRun::sample_keys() {
+    // ---- the first execution of a query shape (nothing remembered, or NQE_NO_PLAN_HINTS): a SAMPLE of the keys picks the starting
+    // tier instead of falling through abandoned ones — the reference's run_sql is one-shot (db.rs:24-37), so the first execution is
+    // the one that counts.  65536 keys (key_sample_kernel, ~20 us): their distinct count is a lower bound of the groups, so a tier it
+    // rules out would certainly have overflowed; their min / max stand in for the full pass over a plain key column (the streaming
+    // kernel checks every key against the range, and a key outside it asks for the exact measurement).
+    no_hints_env = getenv("NQE_NO_PLAN_HINTS") != nullptr; // (read per call: tests switch it)
+    if (!wants_key_sample()) return;
+    BufRef set = dev_alloc(ctx, (size_t(1) << KEY_SAMPLE_SLOTS_LOG2) * 8), so = dev_alloc(ctx, 32);
+    NQE_HIP_CHECK(hipMemsetAsync(set->ptr, 0xFF, (size_t(1) << KEY_SAMPLE_SLOTS_LOG2) * 8, ctx->stream));
+    NQE_HIP_CHECK(hipMemsetAsync(so->ptr, 0xFF, 8, ctx->stream));
+    NQE_HIP_CHECK(hipMemsetAsync(static_cast<char *>(so->ptr) + 8, 0, 24, ctx->stream));
+    launch(ctx, "agg_key_sample", key_sample_kernel, dim3(KEY_SAMPLE / 256), dim3(256), 0, (const uint64_t *)a.key_src.values, in->rows, a.key, key_flip,
+           (unsigned long long *)set->ptr, (unsigned long long *)so->ptr);
+    uint64_t h[4]; // the sample's min and max in sort order (key ^ key_flip), its distinct count, whether it held the empty-slot key
+    NQE_HIP_CHECK(hipMemcpyAsync(h, so->ptr, 32, hipMemcpyDeviceToHost, ctx->stream));
+    sync(ctx);
+    const uint64_t D = h[2] + (h[3] ? 1 : 0);
+    // groups of the whole table from the sample's distinct count: D = G (1 - exp(-S / G)) (uniform keys; skew only lowers it)
+    double G = double(D);
+    if (D > uint64_t(KEY_SAMPLE) / 2) {
+        double lo = double(D), hi = 1e13;
+        for (int it = 0; it < 60; ++it) {
+            const double mid = std::sqrt(lo * hi);
+            (mid * (1.0 - std::exp(-double(KEY_SAMPLE) / mid)) < double(D) ? lo : hi) = mid;
         }
-        if (ctx->agg_hints.size() >= 256) ctx->agg_hints.clear();
-        // between one and two workgroup tables' worth of groups: two key subsets over a direct-mapped table when the sampled range fits two tables
-        // (pick_key_range); otherwise the range tier of the partitioned path when it fits THAT (10^8 rows, 4500-6000 keys spread over 7x their
-        // number: 0.89-0.90 ms per execution against 1.05-1.15 for two HASHED subsets, tools/probe_sparse_groups.py); hashed subsets for the rest
-        const uint64_t sample_span = h[1] >= h[0] ? h[1] - h[0] + 1 : 0;
-        // groups ONE workgroup table takes: every key of a range it addresses directly; three quarters of its slots when it hashes (the kernel's own
-        // limit, AggArgs::lds_limit: linear probing beyond that load costs more than the next tier)
-        const bool one_direct = plain_int_key && !sw.no_key_range && sample_span != 0 && sample_span <= direct_one_limit;
-        const uint64_t one_limit = one_direct ? direct_one_limit : (!sw.lds_load_limit ? range_limit : range_limit * 3 / 4);
-        const bool sub_direct = plain_int_key && !sw.no_key_range && V == 1 && sw.direct_subsets && subsets_ok && sw.subsets_max >= 1 && sample_span != 0 &&
-                                sample_span <= direct_pair_limit;
-        const bool tier_instead = !sub_direct && sw.direct_subsets && range_part_ok && V == 1 && sw.range_tier && plain_int_key && sample_span != 0 &&
-                                  sample_span + sample_span / 128 + 32 < uint64_t(256) * RANGE_TIER_MAX_SLOTS;
-        if (!sub_direct && (D > 2 * one_limit || (D > one_limit && (!subsets_ok || sw.subsets_max < 1 || tier_instead)))) {
-            partition_mode = true; // more distinct keys in the sample than the workgroup tables of the streaming tiers hold
-            cap = std::max(cap, sized_cap);
-            if (G > 800e3) slab_parts_log2 = PARTS_LOG2; // … and more than 256 partitions of one table each
-            ctx->agg_hints[hint_key] = uint8_t(slab_parts_log2 < PARTS_LOG2 ? 16 : 1);
-            if (range_part_ok && part_span == 0 && h[1] >= h[0]) { // the range the partitions are cut from (see part_min / part_span)
-                uint64_t lo = h[0], hi = h[1]; // sort order: key ^ key_flip
-                if (simple_mod_key) {
-                    const uint64_t m1 = a.key.aux[0].abs_lit - 1;
-                    const bool sgn = key_flip != 0;
-                    lo = (sgn && lo < key_flip) ? (uint64_t(0) - m1) ^ key_flip : key_flip; // a negative key in the sample: -(m - 1), else 0
-                    hi = m1 ^ key_flip;
-                } else {
-                    const uint64_t pad = (hi - lo) / 256 + 16;
-                    lo = lo > pad ? lo - pad : 0;
-                    hi = hi < ~uint64_t(0) - pad ? hi + pad : ~uint64_t(0);
-                }
-                if (hi - lo < (uint64_t(PARTS) << 12)) {
-                    part_min = int64_t(lo ^ key_flip);
-                    part_span = hi - lo + 1;
-                    part_range_sampled = true;
-                }
-            }
-        } else if (D > one_limit) {
-            subsets_log2 = 1;
-            cap = std::max(cap, std::min(sized_cap, RANK_MAX_CAP << subsets_log2));
-            ctx->agg_hints[hint_key] = uint8_t(2);
-            if (sub_direct) { // the sample's range (pick_key_range: a direct-mapped table over the two subsets)
-                if (ctx->agg_key_ranges.size() >= 256) ctx->agg_key_ranges.clear();
-                ctx->agg_key_ranges[hint_key] = std::make_pair(int64_t(h[0] ^ key_flip), h[1] >= h[0] ? h[1] - h[0] + 1 : 0ull);
-                range_sampled = true;
-            }
-        } else {
-            ctx->agg_hints.emplace(hint_key, uint8_t(0)); // sampled: the single-pass tier (a later overflow overwrites this)
-            if (plain_int_key && !sw.no_key_range) {
-                // the sample's range: the whole column's when it is as narrow as a workgroup table (checked row by row by the kernel)
-                if (ctx->agg_key_ranges.size() >= 256) ctx->agg_key_ranges.clear();
-                ctx->agg_key_ranges[hint_key] = std::make_pair(int64_t(h[0] ^ key_flip), h[1] >= h[0] ? h[1] - h[0] + 1 : 0ull);
-                range_sampled = true;
-            }
+        G = lo;
+    }
+    start_from_sample(D, G, h[0], h[1]);
+    if (sw.debug)
+        fprintf(stderr, "[nqe] aggregate key sample: distinct %llu of %d -> ~%.3g groups; start partition %d subsets_log2 %d slab_parts_log2 %d\n",
+                (unsigned long long)D, KEY_SAMPLE, G, int(partition_mode), subsets_log2, slab_parts_log2);
+}
+
+// the starting tier for D distinct keys in the sample (~G groups in the table) within [ordmin, ordmax] (sort order), recorded in the memo
+void AggRun::start_from_sample(uint64_t D, double G, uint64_t ordmin, uint64_t ordmax) {
+    // between one and two workgroup tables' worth of groups: two key subsets over a direct-mapped table when the sampled range fits two tables
+    // (pick_key_range); otherwise the range tier of the partitioned path when it fits THAT (10^8 rows, 4500-6000 keys spread over 7x their
+    // number: 0.89-0.90 ms per execution against 1.05-1.15 for two HASHED subsets, tools/probe_sparse_groups.py); hashed subsets for the rest
+    const uint64_t sample_span = ordmax >= ordmin ? ordmax - ordmin + 1 : 0;
+    const int64_t sample_min = int64_t(ordmin ^ key_flip);
+    // groups ONE workgroup table takes: every key of a range it addresses directly; three quarters of its slots when it hashes (the kernel's own
+    // limit, AggArgs::lds_limit: linear probing beyond that load costs more than the next tier)
+    const bool one_direct = plain_int_key && sample_span != 0 && sample_span <= direct_one_limit;
+    const uint64_t one_limit = one_direct ? direct_one_limit : range_limit * 3 / 4;
+    const bool sub_direct = plain_int_key && V == 1 && subsets_ok && sample_span != 0 && sample_span <= direct_pair_limit;
+    const bool tier_instead = !sub_direct && range_part_ok && V == 1 && plain_int_key && sample_span != 0 && sample_span + sample_span / 128 + 32 < uint64_t(256) * RANGE_TIER_MAX_SLOTS;
+    if (!sub_direct && (D > 2 * one_limit || (D > one_limit && (!subsets_ok || tier_instead)))) {
+        go_partitioned(); // more distinct keys in the sample than the workgroup tables of the streaming tiers hold
+        if (G > 800e3) slab_parts_log2 = PARTS_LOG2; // … and more than 256 partitions of one table each
+        memo().remember_start(slab_start(), false);
+        if (range_part_ok && part_span == 0 && ordmax >= ordmin) part_range_from_sample(ordmin, ordmax);
+    } else if (D > one_limit) {
+        subsets_log2 = 1;
+        grow_cap_for_subsets(subsets_log2);
+        memo().remember_start(AggStart::TwoSubsets, false);
+        if (sub_direct) { // the sample's range (pick_key_range: a direct-mapped table over the two subsets)
+            memo().remember_key_range(sample_min, sample_span);
+            range_sampled = true;
         }
-        if (sw.debug)
-            fprintf(stderr, "[nqe] aggregate key sample: distinct %llu of %d -> ~%.3g groups; start partition %d subsets_log2 %d slab_parts_log2 %d\n",
-                    (unsigned long long)D, KEY_SAMPLE, G, int(partition_mode), subsets_log2, slab_parts_log2);
+    } else {
+        memo().remember_sampled_streaming(); // sampled: the single-pass tier (a later overflow overwrites this)
+        if (plain_int_key) {
+            // the sample's range: the whole column's when it is as narrow as a workgroup table (checked row by row by the kernel)
+            memo().remember_key_range(sample_min, sample_span);
+            range_sampled = true;
+        }
+    }
+}
+
+// the range the key-range partitions are cut from (see part_min / part_span), from the sample's [lo, hi] in sort order
+void AggRun::part_range_from_sample(uint64_t lo, uint64_t hi) {
+    if (simple_mod_key()) {
+        const uint64_t m1 = a.key.aux[0].abs_lit - 1;
+        const bool sgn = key_flip != 0;
+        lo = (sgn && lo < key_flip) ? (uint64_t(0) - m1) ^ key_flip : key_flip; // a negative key in the sample: -(m - 1), else 0
+        hi = m1 ^ key_flip;
+    } else {
+        const uint64_t pad = (hi - lo) / 256 + 16;
+        lo = lo > pad ? lo - pad : 0;
+        hi = hi < ~uint64_t(0) - pad ? hi + pad : ~uint64_t(0);
+    }
+    if (hi - lo < (uint64_t(PARTS) << 12)) {
+        part_min = int64_t(lo ^ key_flip);
+        part_span = hi - lo + 1;
+        part_range_sampled = true;
     }
 }
 
 void AggRun::pick_key_range() {
     // (round 5: also under key subsets — two workgroups per row range, each holding one half of a range of up to 2 x 4096 values in a
     // direct-mapped table (AggArgs::direct_sub_width): one value column)
-    const bool sub_range = subsets_log2 == 1 && subsets_ok && V == 1 && sw.direct_subsets;
-    if (hint_key && !sw.no_key_range && !partition_mode && (subsets_log2 == 0 || sub_range) && (!no_hints_env || range_sampled) && plain_int_key) {
+    const bool sub_range = subsets_log2 == 1 && subsets_ok && V == 1;
+    // (NQE_NO_PLAN_HINTS: only a range this call sampled)
+    if (hint_key && !partition_mode && (subsets_log2 == 0 || sub_range) && (!no_hints_env || range_sampled) && plain_int_key) {
         // `group by k`, k a plain integer column (dictionary codes, small ids): a value range that fits a workgroup table makes the
         // streaming kernel address it by key - min (no hash, no probe sequence, replicas for a handful of groups).  The range comes
         // from the first execution's key sample, or — tables too small to sample, queries with a predicate — from one pass over the
-        // column, and is remembered (nqe_ctx::agg_key_ranges)
-        auto rt = ctx->agg_key_ranges.find(hint_key);
-        if (rt == ctx->agg_key_ranges.end()) {
-            if (ctx->agg_key_ranges.size() >= 256) ctx->agg_key_ranges.clear();
-            rt = ctx->agg_key_ranges.emplace(hint_key, measure_key_range()).first;
+        // column, and is remembered (AggMemo::key_range_known)
+        if (!memo().key_range_known) {
+            const auto exact = measure_key_range();
+            memo().remember_key_range(exact.first, exact.second);
         }
-        if (rt->second.second != 0 && rt->second.second <= one_table_or_subsets_limit()) {
-            range_on = true;
-            range_min = rt->second.first;
-            range_span = rt->second.second;
-            if (range_span > range_limit && subsets_log2 == 0) cap = std::max(cap, std::min(sized_cap, RANK_MAX_CAP << 1)); // (room in the group table should the fold go through it)
+        const AggMemo &m = memo();
+        if (m.key_span != 0 && m.key_span <= one_table_or_subsets_limit()) {
+            adopt_key_range(m.key_min, m.key_span);
+            if (range_span > range_limit && subsets_log2 == 0) grow_cap_for_subsets(1); // (room in the group table should the fold go through it)
         }
     }
     if (!subsets_ok) subsets_log2 = 0;
@@ -1251,112 +895,16 @@ PassStatus AggRun::shape_pass() {
     blocks_per_cu = shmem <= 80 * 1024 ? 2 : 1;
     grid = int(std::min<int64_t>(int64_t(ctx->num_cus) * blocks_per_cu,
                                      (in->rows + int64_t(AGG_BLOCK) * AGG_U - 1) / (int64_t(AGG_BLOCK) * AGG_U)));
-    kk = 2, fast_key = -1; // kk: general-kernel key kind; fast_key: fast-kernel key kind (-1 = not covered)
-    if (a.key.nops == 0) kk = 0, fast_key = 0;
-    else if (a.key.nops == 1 && a.key.op[0] == NQE_OP_MODULOS && !a.key.lit_left[0] &&
-             (a.key.op_dtype[0] == NQE_INT64 || a.key.op_dtype[0] == NQE_UINT64)) {
-        if (a.key.aux[0].pow2_shift >= 0) kk = 1, fast_key = 1;
-        else if (a.key.aux[0].more >= 0) fast_key = 2; // `col % d`, d not a power of two: magic multiply
-    }
-    if (fast_key < 0 && a.key.nops >= 1) {
-        // any other chain of integer arithmetic with literals that cannot fault (divisors: literals other than 0
-        // and -1): the fast kernels evaluate it with the generic interpreter (KEY = 3)
-        bool ok = true;
-        for (int k = 0; k < a.key.nops; ++k) {
-            const int op = a.key.op[k];
-            ok = ok && op >= NQE_OP_PLUS && op <= NQE_OP_MODULOS && (a.key.op_dtype[k] == NQE_INT64 || a.key.op_dtype[k] == NQE_UINT64);
-            if (op == NQE_OP_DIVIDE || op == NQE_OP_MODULOS)
-                ok = ok && !a.key.lit_left[k] && a.key.lit[k] != 0 && a.key.lit[k] != ~0ull;
-        }
-        if (ok) fast_key = 3;
-    }
-    // ---- `A and B [and …]` / `A or B [or …]` of up to four range tests (pred_mode 3): inside the single-pass streaming kernel when everything it
-    // reads is a plain 8-byte column; everywhere else (more groups than one workgroup table, validity bitmaps, a key the
-    // kernel does not compute) the predicate is materialised as a Boolean column first, as any other tree is
+    classify_key();
     if (a.pred_mode == 1 && a.nv > 1 && a.pred.nops > 1) {
         // a chain with Float64 steps is interpreted by the one-value-column instances only
         bool f64_steps = false;
         for (int k = 0; k < a.pred.nops; ++k) f64_steps = f64_steps || a.pred.op_dtype[k] == NQE_FLOAT64;
         if (f64_steps) materialize_pred();
     }
-    if (a.pred_mode == 3) {
-        bool ok = !partition_mode && subsets_log2 == 0 && fast_key >= 0 && a.nv >= 1 && is_word_type(a.key_src.dtype) && !a.key_src.valid;
-        // (the general form — tests with an arithmetic step, nested and/or — runs in the PRED = 5 instances: one value
-        // column per pass, built-in key shapes)
-        if (a.conj.general) ok = ok && a.nv == 1 && fast_key != 3;
-        for (int j = 0; j < a.nv; ++j) ok = ok && a.val[j].values && !a.val[j].valid;
-        const void *other = nullptr; // the one column the kernel would load for the predicate alone
-        if (ok) {
-            a.conj.need_pw = 0;
-            for (int t = 0; t < a.conj.n; ++t) {
-                const DevColumn &lc = in->cols[size_t(conj_col[t])];
-                const void *lp = lc.values->ptr;
-                if (lp == a.key_src.values) a.conj.t[t].src = 0;
-                else if (lp == a.val[0].values) a.conj.t[t].src = 1;
-                else {
-                    if (other && other != lp) ok = false; // two such columns: not this kernel's shape
-                    other = lp;
-                    a.conj.t[t].src = 2;
-                    a.conj.need_pw = 1;
-                    a.pred_src = src_of(lc);
-                }
-            }
-        }
-        if (!ok) materialize_pred();
-    }
-    // ---- any other fault-free tree over the same columns (pred_mode 4): the stack machine inside the streaming kernel
-    if (a.pred_mode == 4) {
-        // (instances: one value column per pass, built-in key shapes — the stack machine's registers)
-        bool ok = !partition_mode && subsets_log2 == 0 && fast_key >= 0 && fast_key != 3 && a.nv == 1 && is_word_type(a.key_src.dtype) && !a.key_src.valid;
-        for (int j = 0; j < a.nv; ++j) ok = ok && a.val[j].values && !a.val[j].valid;
-        TreePred tp = tree;
-        const void *other = nullptr;
-        int slot_of[TREE_MAX_COLS] = {0, 0, 0};
-        a.tree_need_pw = 0;
-        for (int c = 0; ok && c < tree.ncols; ++c) {
-            const DevColumn &lc = in->cols[size_t(tree.col[c])];
-            const void *lp = lc.values->ptr;
-            if (lp == a.key_src.values) slot_of[c] = 0;
-            else if (lp == a.val[0].values) slot_of[c] = 1;
-            else {
-                if (other && other != lp) ok = false; // two such columns: not this kernel's shape
-                other = lp;
-                slot_of[c] = 2;
-                a.tree_need_pw = 1;
-                a.pred_src = src_of(lc);
-            }
-        }
-        if (ok) {
-            for (int i = 0; i < tp.n; ++i) {
-                if (tp.ins[i].a_src >= TS_W0) tp.ins[i].a_src = TS_W0 + slot_of[tp.ins[i].a_src - TS_W0];
-                if (tp.ins[i].b_src >= TS_W0) tp.ins[i].b_src = TS_W0 + slot_of[tp.ins[i].b_src - TS_W0];
-            }
-            tree_buf = dev_alloc(ctx, sizeof(TreeInstr) * TREE_MAX_INSTR);
-            launch(ctx, "agg_store_tree", store_tree_kernel, dim3(1), dim3(64), 0, tp, (TreeInstr *)tree_buf->ptr);
-            a.tree_prog = reinterpret_cast<uint64_t>(tree_buf->ptr);
-            a.tree_n = tp.n;
-        } else
-            materialize_pred();
-    }
-    // ---- kernel variant (see the template comment)
-    pk = 0;
-    ka = a;
-    if (a.pred_mode == 2) pk = 2;
-    else if (a.pred_mode == 3) pk = a.conj.general ? 5 : 4;
-    else if (a.pred_mode == 4) pk = 6;
-    else if (a.pred_mode == 1) {
-        const SimpleExpr &pe = a.pred;
-        pk = 3;
-        if (pe.nops == 1 && pe.op[0] <= NQE_OP_GT_EQ && is_word_type(pe.src_dtype)) {
-            pk = 1;
-            if (pe.lit_left[0]) { // lit op x  ≡  x op' lit
-                static const int flip[6] = {NQE_OP_EQ, NQE_OP_NOT_EQ, NQE_OP_GT, NQE_OP_GT_EQ, NQE_OP_LT, NQE_OP_LT_EQ};
-                ka.pred.op[0] = flip[pe.op[0]];
-                ka.pred.lit_left[0] = 0;
-            }
-        }
-    }
-    if (pk == 5) ka.tree_need_pw = a.conj.need_pw; // (the interpreted-predicate instances load the third word on this flag)
+    if (a.pred_mode == 3) resolve_list_pred();
+    if (a.pred_mode == 4) resolve_tree_pred();
+    pick_pred_variant();
     plain = is_word_type(a.key_src.dtype);
     // a Boolean predicate column without nulls (a Boolean input column, or any predicate tree evaluated by the
     // expression machine) is tested by the same variants as a separate integer predicate column: the word of a
@@ -1378,7 +926,127 @@ PassStatus AggRun::shape_pass() {
     fpred = FastPred{};
     if (bitmap_pred) fpred = bitmap_fast_pred();
     range_pred = pk == 1 && make_fast_pred(a.pred, &fpred);
-    // any other fault-free integer chain `col op lit [op lit]` ending in a comparison: interpreted inside the fast kernel
+    classify_chain_pred();
+    fast = plain && a.nv >= 1 && fast_key >= 0 && (pk == 0 || pk >= 4 || bitmap_pred || range_pred || chain_pred);
+    if (pk >= 4 && (!fast || vnull)) fail(NQE_ERR_NOT_SUPPORTED, "internal: a tree predicate reached a kernel that cannot evaluate it");
+    if (a.nv == NVMAX) {
+        // the three-column instances: no predicate or a range test on the key column, the built-in key shapes, no validity
+        const bool key_range = pk == 1 && range_pred && a.pred_shares_key && !bitmap_pred && !fpred.fmask;
+        if (!(fast && (pk == 0 || key_range) && fast_key != 3 && !vnull && !partition_mode)) {
+            three_on = false;
+            three_redo = true;
+            return PassStatus::Abort;
+        }
+    }
+    return PassStatus::Done;
+}
+
+// the key's kind for the general kernel (kk) and for the fast kernels (fast_key; -1: not covered)
+void AggRun::classify_key() {
+    kk = 2, fast_key = -1;
+    if (a.key.nops == 0) kk = 0, fast_key = 0;
+    else if (a.key.nops == 1 && a.key.op[0] == NQE_OP_MODULOS && !a.key.lit_left[0] &&
+             (a.key.op_dtype[0] == NQE_INT64 || a.key.op_dtype[0] == NQE_UINT64)) {
+        if (a.key.aux[0].pow2_shift >= 0) kk = 1, fast_key = 1;
+        else if (a.key.aux[0].more >= 0) fast_key = 2; // `col % d`, d not a power of two: magic multiply
+    }
+    if (fast_key < 0 && a.key.nops >= 1) {
+        // any other chain of integer arithmetic with literals that cannot fault (divisors: literals other than 0
+        // and -1): the fast kernels evaluate it with the generic interpreter (KEY = 3)
+        bool ok = true;
+        for (int k = 0; k < a.key.nops; ++k) {
+            const int op = a.key.op[k];
+            ok = ok && op >= NQE_OP_PLUS && op <= NQE_OP_MODULOS && (a.key.op_dtype[k] == NQE_INT64 || a.key.op_dtype[k] == NQE_UINT64);
+            if (op == NQE_OP_DIVIDE || op == NQE_OP_MODULOS)
+                ok = ok && !a.key.lit_left[k] && a.key.lit[k] != 0 && a.key.lit[k] != ~0ull;
+        }
+        if (ok) fast_key = 3;
+    }
+}
+
+// which of the words the streaming kernel loads per row holds column `c` of the predicate: 0 the key's, 1 the first value column's, 2 the one
+// column the kernel would load for the predicate alone (noted in a.pred_src).  A second such column: not this kernel's shape (ok = false)
+int AggRun::pred_word_of(const DevColumn &c, const void *&other, bool &ok) {
+    const void *p = c.values->ptr;
+    if (p == a.key_src.values) return 0;
+    if (p == a.val[0].values) return 1;
+    if (other && other != p) ok = false;
+    other = p;
+    a.pred_src = src_of(c);
+    return 2;
+}
+
+// ---- `A and B [and …]` / `A or B [or …]` of up to four range tests (pred_mode 3): inside the single-pass streaming kernel when everything it
+// reads is a plain 8-byte column; everywhere else (more groups than one workgroup table, validity bitmaps, a key the
+// kernel does not compute) the predicate is materialised as a Boolean column first, as any other tree is
+void AggRun::resolve_list_pred() {
+    bool ok = !partition_mode && subsets_log2 == 0 && fast_key >= 0 && a.nv >= 1 && is_word_type(a.key_src.dtype) && !a.key_src.valid;
+    // (the general form — tests with an arithmetic step, nested and/or — runs in the PRED = 5 instances: one value
+    // column per pass, built-in key shapes)
+    if (a.conj.general) ok = ok && a.nv == 1 && fast_key != 3;
+    for (int j = 0; j < a.nv; ++j) ok = ok && a.val[j].values && !a.val[j].valid;
+    const void *other = nullptr;
+    if (ok) {
+        a.conj.need_pw = 0;
+        for (int t = 0; t < a.conj.n; ++t) {
+            a.conj.t[t].src = pred_word_of(in->cols[size_t(conj_col[t])], other, ok);
+            if (a.conj.t[t].src == 2) a.conj.need_pw = 1;
+        }
+    }
+    if (!ok) materialize_pred();
+}
+
+// ---- any other fault-free tree over the same columns (pred_mode 4): the stack machine inside the streaming kernel
+void AggRun::resolve_tree_pred() {
+    // (instances: one value column per pass, built-in key shapes — the stack machine's registers)
+    bool ok = !partition_mode && subsets_log2 == 0 && fast_key >= 0 && fast_key != 3 && a.nv == 1 && is_word_type(a.key_src.dtype) && !a.key_src.valid;
+    for (int j = 0; j < a.nv; ++j) ok = ok && a.val[j].values && !a.val[j].valid;
+    TreePred tp = tree;
+    const void *other = nullptr;
+    int slot_of[TREE_MAX_COLS] = {0, 0, 0};
+    a.tree_need_pw = 0;
+    for (int c = 0; ok && c < tree.ncols; ++c) {
+        slot_of[c] = pred_word_of(in->cols[size_t(tree.col[c])], other, ok);
+        if (slot_of[c] == 2) a.tree_need_pw = 1;
+    }
+    if (!ok) {
+        materialize_pred();
+        return;
+    }
+    for (int i = 0; i < tp.n; ++i) {
+        if (tp.ins[i].a_src >= TS_W0) tp.ins[i].a_src = TS_W0 + slot_of[tp.ins[i].a_src - TS_W0];
+        if (tp.ins[i].b_src >= TS_W0) tp.ins[i].b_src = TS_W0 + slot_of[tp.ins[i].b_src - TS_W0];
+    }
+    tree_buf = dev_alloc(ctx, sizeof(TreeInstr) * TREE_MAX_INSTR);
+    launch(ctx, "agg_store_tree", store_tree_kernel, dim3(1), dim3(64), 0, tp, (TreeInstr *)tree_buf->ptr);
+    a.tree_prog = reinterpret_cast<uint64_t>(tree_buf->ptr);
+    a.tree_n = tp.n;
+}
+
+// ---- kernel variant (see the template comment): pk, and the pass's copy of the arguments (ka)
+void AggRun::pick_pred_variant() {
+    pk = 0;
+    ka = a;
+    if (a.pred_mode == 2) pk = 2;
+    else if (a.pred_mode == 3) pk = a.conj.general ? 5 : 4;
+    else if (a.pred_mode == 4) pk = 6;
+    else if (a.pred_mode == 1) {
+        const SimpleExpr &pe = a.pred;
+        pk = 3;
+        if (pe.nops == 1 && pe.op[0] <= NQE_OP_GT_EQ && is_word_type(pe.src_dtype)) {
+            pk = 1;
+            if (pe.lit_left[0]) { // lit op x  ≡  x op' lit
+                static const int flip[6] = {NQE_OP_EQ, NQE_OP_NOT_EQ, NQE_OP_GT, NQE_OP_GT_EQ, NQE_OP_LT, NQE_OP_LT_EQ};
+                ka.pred.op[0] = flip[pe.op[0]];
+                ka.pred.lit_left[0] = 0;
+            }
+        }
+    }
+    if (pk == 5) ka.tree_need_pw = a.conj.need_pw; // (the interpreted-predicate instances load the third word on this flag)
+}
+
+// any other fault-free integer chain `col op lit [op lit]` ending in a comparison: interpreted inside the fast kernel
+void AggRun::classify_chain_pred() {
     chain_pred = false;
     if (a.pred_mode == 1 && !bitmap_pred && !range_pred && a.pred.nops >= 1 &&
         a.pred.op[a.pred.nops - 1] <= NQE_OP_GT_EQ) {
@@ -1397,18 +1065,6 @@ PassStatus AggRun::shape_pass() {
             }
         }
     }
-    fast = plain && a.nv >= 1 && fast_key >= 0 && (pk == 0 || pk >= 4 || bitmap_pred || range_pred || chain_pred);
-    if (pk >= 4 && (!fast || vnull)) fail(NQE_ERR_NOT_SUPPORTED, "internal: a tree predicate reached a kernel that cannot evaluate it");
-    if (a.nv == NVMAX) {
-        // the three-column instances: no predicate or a range test on the key column, the built-in key shapes, no validity
-        const bool key_range = pk == 1 && range_pred && a.pred_shares_key && !bitmap_pred && !fpred.fmask;
-        if (!(fast && (pk == 0 || key_range) && fast_key != 3 && !vnull && !partition_mode)) {
-            three_on = false;
-            three_redo = true;
-            return PassStatus::Abort;
-        }
-    }
-    return PassStatus::Done;
 }
 
 // ---- partitioned path, slab form
@@ -1422,24 +1078,14 @@ PassStatus AggRun::tier_slab() {
     const bool k32 = a.nv == 1 && (!key32_failed || range_part);
     const int rpt = k32 ? slab_scatter_soa_rows_per_thread() : slab_scatter_rows_per_thread(fp, fast_key, a.nv);
     // the two-stream form runs 512-thread workgroups, two per CU: their barrier phases overlap
-    const int sc_threads = k32 ? sw.soa_threads : AGG_BLOCK, sc_per_cu = k32 ? 1024 / sw.soa_threads : slab_scatter_wg_per_cu();
+    const int sc_threads = k32 ? SOA_THREADS : AGG_BLOCK, sc_per_cu = k32 ? 1024 / SOA_THREADS : slab_scatter_wg_per_cu();
     const int64_t tile_rows = int64_t(sc_threads) * rpt;
     int W = int(std::min<int64_t>(int64_t(ctx->num_cus) * sc_per_cu, (in->rows + tile_rows - 1) / tile_rows));
     int64_t chunk = ((in->rows + W - 1) / W + tile_rows - 1) / tile_rows * tile_rows;
     W = int((in->rows + chunk - 1) / chunk);
-    int sparts_log2 = slab_parts_log2;
-    // (a table of the range tier may hold up to 5120 slots — 28 bytes each, 140 KB of LDS: a SAMPLED range of 2^20 keys is padded by 1/256
-    // and would otherwise need 512 partitions on the first execution: 1.58 instead of ~1.0 ms per 10^8 rows)
-    const bool tier_wanted = range_part && V == 1 && sw.range_tier;
-    if (range_part) sparts_log2 = part_span <= (uint64_t(256) * (tier_wanted ? RANGE_TIER_MAX_SLOTS : 4096)) ? 8 : PARTS_LOG2;
-    // the range tier (aggregate_common.hpp: RangeRec): as many partitions as the RANGE needs at 2^range_slots_log2 slots per table (16 .. 256;
-    // 512 beyond 2^20 values), several workgroups per partition in the second kernel, the transposing tail.  One value column (V == 1).
-    const bool range_tier = tier_wanted;
-    if (range_tier && sparts_log2 == 8) {
-        int need = 4;
-        while (need < 8 && (uint64_t(1) << (need + sw.range_slots_log2)) < part_span) ++need;
-        sparts_log2 = need;
-    }
+    // the range tier (aggregate_common.hpp: RangeRec): several workgroups per partition in the second kernel, the transposing tail.  One value column
+    const bool range_tier = range_part && V == 1;
+    const int sparts_log2 = slab_partitions_log2(range_part, range_tier);
     const int used_parts = 1 << sparts_log2;
     const uint64_t rslots = range_part ? (part_span + (uint64_t(1) << sparts_log2) - 1) >> sparts_log2 : 0;
     range_part_used = range_part;
@@ -1465,7 +1111,7 @@ PassStatus AggRun::tier_slab() {
     } catch (const Error &e) {
         if (e.code != NQE_ERR_OUT_OF_MEMORY) throw;
         slab_failed = true;
-        if (hint_key) ctx->agg_hints[hint_key] = uint8_t(17 | (key32_failed ? 0x40 : 0)); // partitioned, exact form: do not try the slabs again
+        if (hint_key) memo().remember_start(AggStart::ExactForm, key32_failed); // do not try the slabs again
         flags_reset(ctx);
         slab_oom = true;
         return PassStatus::Abort;
@@ -1487,12 +1133,7 @@ PassStatus AggRun::tier_slab() {
     AggArgs sa = ka;
     size_t sshmem = shmem;
     int sblocks = blocks_per_cu;
-    if (a.nv == 1) { // one value column: a 4096-slot table (147 KB, one workgroup per CU) doubles the distinct keys a partition may hold
-        sa.lds_cap = 4096;
-        sa.lds_shift = 64 - 12;
-        sshmem = ((size_t(4097) * (8 + 28)) + 15) / 16 * 16;
-        sblocks = 1;
-    }
+    if (a.nv == 1) one_column_table(sa, sshmem, &sblocks);
     if (range_tier) {
         range_tail(sa, sl, uint32_t(rslots));
         // (the slabs go back to the pool when this scope ends: whatever takes them next runs behind these kernels on the same stream)
@@ -1508,6 +1149,19 @@ PassStatus AggRun::tier_slab() {
                sa, sl, tb.g, ctx->d_flags);
     sync(ctx); // the slabs are released at the end of this scope
     return PassStatus::Done;
+}
+
+// log2 of the partitions of a slab attempt: what the ladder has arrived at for hashed partitions; what the RANGE needs for key-range ones
+int AggRun::slab_partitions_log2(bool range_part, bool range_tier) const {
+    if (!range_part) return slab_parts_log2;
+    // (a table of the range tier may hold up to 5120 slots — 28 bytes each, 140 KB of LDS: a SAMPLED range of 2^20 keys is padded by 1/256
+    // and would otherwise need 512 partitions on the first execution: 1.58 instead of ~1.0 ms per 10^8 rows)
+    if (part_span > uint64_t(256) * (range_tier ? RANGE_TIER_MAX_SLOTS : 4096)) return PARTS_LOG2;
+    if (!range_tier) return 8;
+    // the range tier: as many partitions as the range needs at 2^RANGE_SLOTS_LOG2 slots per table (16 .. 256; 512 beyond 2^20 values)
+    int need = 4;
+    while (need < 8 && (uint64_t(1) << (need + RANGE_SLOTS_LOG2)) < part_span) ++need;
+    return need;
 }
 
 // the range tier behind its scatter: Q workgroups per partition aggregate the slabs into whole tables, the transposing tail ranks and
@@ -1536,7 +1190,7 @@ void AggRun::range_emit(int parts_log2, int Q, uint32_t rslots, uint64_t span, i
     ranged.keys->rows = room;
     ranged.keys->cols.push_back(make_word_column(ctx, kinfo.out_dtype, room, false));
     // keys per thread of the tail: 4096-key blocks for wide ranges, 1024-key blocks to keep narrow ones parallel
-    const int items = sw.range_emit_items ? sw.range_emit_items : (span >= (uint64_t(1) << 19) ? 4 : 1);
+    const int items = span >= RANGE_EMIT_WIDE_SPAN ? 4 : 1;
     const uint32_t kb = uint32_t(RE_BLOCK * items), sb = std::max<uint32_t>(1u, kb >> parts_log2), nblocks = (rslots + sb - 1) / sb;
     // block statuses (ticket + one word per block), then three zeroed words for the host: the group count, ~(first key - key_min), last key - key_min
     range_status = dev_alloc(ctx, (size_t(nblocks) + 2 + 4) * 8);
@@ -1584,16 +1238,10 @@ void AggRun::tier_exact() {
         const size_t sc_shmem = sc_rows * 8 * size_t(1 + a.nv) + size_t(PARTS) * (8 + 4 + 4);
         launch(ctx, "agg_partition_scatter", pick_scatter_kernel(fp, fast_key, a.nv), dim3(nblk), dim3(AGG_BLOCK), sc_shmem, ka, fpred,
                pa);
-        // one value column: a 4096-slot table (147 KB, one workgroup per CU) doubles the distinct keys a partition may hold
         AggArgs sa = ka;
         size_t sshmem = shmem;
         int sblocks = blocks_per_cu;
-        if (a.nv == 1) {
-            sa.lds_cap = 4096;
-            sa.lds_shift = 64 - 12;
-            sshmem = ((size_t(4097) * (8 + 28)) + 15) / 16 * 16;
-            sblocks = 1;
-        }
+        if (a.nv == 1) one_column_table(sa, sshmem, &sblocks);
         int sgrid = std::min(PARTS, ctx->num_cus * sblocks);
         auto segk = pick_segments_kernel(a.nv, vf64);
         if (!level2) {
@@ -1624,19 +1272,28 @@ PassStatus AggRun::tier_streaming(int v0) {
     // asking before the partition kernels had that variant: a densely laid out table went to the hashed general kernel)
     ka.allow_partition = in->rows >= (int64_t(1) << 18) ? 1 : 0;
     asked_partition = asked_partition || ka.allow_partition != 0;
-    ka.flag_check_mask = sw.flag_check_mask; // how often a wave looks at the overflow flags (aggregate_common.hpp): every 8th iteration
+    ka.flag_check_mask = FLAG_CHECK_MASK; // how often a wave looks at the overflow flags (aggregate_common.hpp)
+    shape_direct_table();
+    if (try_register_kernel() || try_specialised_kernel(v0)) return PassStatus::Done;
+    if (jit_whole) {
+        jit_redo = true; // (cannot happen once the dry run said yes — but a static kernel must never run without the predicate)
+        return PassStatus::Abort;
+    }
+    launch_fast_kernel();
+    return PassStatus::Done;
+}
+
+// the launch shape of the streaming tier (fgrid, fshmem) and its workgroup table (ka.lds_cap, ka.direct*: hashed, or addressed directly by
+// `… % m` or by key - min of a measured range, replicated, split over two key subsets), and which instance family reads it (share, nomm)
+void AggRun::shape_direct_table() {
     // ONE 1024-thread workgroup per CU: fewer concurrent streams read HBM faster (A/B on one box: headline
     // 2.44 -> 2.39 ms, C3 2.56 -> 2.41 ms, random keys 3.63 -> 3.54 ms, 1 % nulls 0.81 -> 0.69 ms per 2e8 rows;
     // tools/stream_bench.hip shows the same for a bare read kernel)
-    int fgrid = std::min(grid, ctx->num_cus);
+    fgrid = std::min(grid, ctx->num_cus);
     ka.subsets_log2 = subsets_log2;
     if (subsets_log2) fgrid = std::max(1, ctx->num_cus / (8 << subsets_log2)) * (8 << subsets_log2);
-    size_t fshmem = shmem;
-    if (a.nv == 1) { // the CU's LDS is this workgroup's alone: a 4096-slot table (147 KB) keeps up to ~3500 groups on this path
-        ka.lds_cap = 4096;
-        ka.lds_shift = 64 - 12;
-        fshmem = ((size_t(4097) * (8 + 28)) + 15) / 16 * 16;
-    }
+    fshmem = shmem;
+    if (a.nv == 1) one_column_table(ka, fshmem); // (the CU's LDS is this workgroup's alone: 4096 slots keep up to ~3500 groups on this path)
     // (round 6) a directly addressed table without validity bitmaps has no key words: up to DIRECT_WIDE_SLOTS keys in ONE workgroup table
     // nomm1: one value column nobody asks min / max of, through the instance without those arrays (12 instead of 28 bytes per slot)
     const bool nomm_ok = a.nv == 1 && !a.need_minmax[0] && !vnull && (fp == 0 || fp == 1) && fast_key != 3;
@@ -1663,7 +1320,7 @@ PassStatus AggRun::tier_streaming(int v0) {
         }
     }
     ka.direct_sub_width = 0;
-    ka.lds_limit = (ka.allow_partition && sw.lds_load_limit) ? uint32_t(ka.lds_cap) * 3u / 4u : 0u; // (hashed tables only look at it)
+    ka.lds_limit = ka.allow_partition ? uint32_t(ka.lds_cap) * 3u / 4u : 0u; // (hashed tables only look at it)
     // two subsets over a measured range: its two halves (whole 16-slot units), each a table without key words
     const uint64_t half_span = ((range_span + 1) / 2 + 15) & ~uint64_t(15);
     const bool pair_fits = subsets_log2 == 1 && a.nv == 1 && !vnull && range_span <= direct_pair_limit && half_span <= (pair_nomm ? DIRECT_WIDE_SLOTS_NOMM : DIRECT_WIDE_SLOTS);
@@ -1690,69 +1347,71 @@ PassStatus AggRun::tier_streaming(int v0) {
     ka.subset_shift = ka.lds_shift - 3; // the bits below the table's slot bits (subsets_log2 <= 3)
     // the value column is the key column itself (and the predicate, if any, tests it too): the single-load instance
     // (three columns: the instance whose tile leaves the first value column out because it IS the key column)
-    const bool share = (a.nv == 1 || a.nv == NVMAX) && a.val_shares_key[0] && a.val[0].values == a.key_src.values && (fp == 0 || fp == 1) && fast_key != 3 &&
+    share = (a.nv == 1 || a.nv == NVMAX) && a.val_shares_key[0] && a.val[0].values == a.key_src.values && (fp == 0 || fp == 1) && fast_key != 3 &&
                        !vnull && (a.nv == NVMAX || !vf64) && subsets_log2 == 0;
     // no aggregate of the pass asks for min / max: instances without those LDS arrays (two and three columns, and the
     // single-load one — `count(id) … group by id % 3` updates one LDS word per row instead of reading two and updating four)
-    bool nomm = a.nv >= 2 || share || nomm1 || nomm_sub;
+    nomm = a.nv >= 2 || share || nomm1 || nomm_sub;
     for (int j = 0; j < a.nv; ++j) nomm = nomm && !a.need_minmax[j];
-    // a predicate tree the static kernel would interpret (PRED 5 / 6) over `col % m` keys and one value column: the lean
-    // run-time specialised kernel, once it has been compiled — its workgroup tables are folded into the group table here
-    // interpreted chain predicates (PRED 3: `id % 10 < 5`, `id * 3 >= K`) take the specialised kernel too: 0.70 -> 0.555 ms per 2x10^8 rows
-    // ---- `col % m`, m <= 4 (the reference's own `group by id % 3`): the register-resident kernel (aggregate_tiny.hip) — no LDS table at all
-    {
-        const uint64_t tm = a.key.nops == 1 ? a.key.aux[0].abs_lit : 0;
-        bool tiny = sw.tiny_groups && tiny_ok && !jit_whole && ka.direct == 1 && (fast_key == 1 || fast_key == 2) && tm >= 1 && tm <= 4 && (fp == 0 || fp == 1) && !vnull &&
-                    subsets_log2 == 0 && key_col >= 0 && a.nv >= 1 && a.nv <= 3 && in->rows >= (int64_t(1) << 20);
-        for (int j = 0; tiny && j < a.nv; ++j) tiny = a.val[j].values != nullptr && (j == a.nv - 1 || !a.need_minmax[j]);
-        // (its tiles are read in 16-byte loads: a column that starts on an odd word — a slice of a borrowed buffer — takes the streaming kernel)
-        tiny = tiny && (reinterpret_cast<uintptr_t>(a.key_src.values) & 15u) == 0;
-        for (int j = 0; tiny && j < a.nv; ++j) tiny = (reinterpret_cast<uintptr_t>(a.val[j].values) & 15u) == 0;
-        if (tiny) {
-            const size_t cells = size_t(fgrid) * size_t(tm), col_words = (cells * 28 + 7) / 8;
-            BufRef partials = dev_alloc(ctx, col_words * 8 * size_t(a.nv) + 64);
-            ka.partials = reinterpret_cast<uint64_t>(partials->ptr);
-            ka.partial_span = uint32_t(tm);
-            const bool mm = a.need_minmax[a.nv - 1] != 0;
-            launch(ctx, "agg_grouped_tiny", pick_tiny_groups_kernel(fp, a.nv, mm, uint32_t(tm), a.val[0].values == a.key_src.values), dim3(fgrid), dim3(AGG_BLOCK), 0, ka, fpred, uint32_t(tm), uint32_t(sw.tiny_unpack_tiles), ctx->d_flags);
-            for (int j = 0; j < a.nv; ++j) {
-                const double *ps = reinterpret_cast<const double *>(partials->ptr) + size_t(j) * col_words;
-                launch(ctx, "agg_fold_partials", agg_fold_partials_kernel, dim3((unsigned(tm) + 15) / 16), dim3(256), 0, ps, ps + cells, ps + 2 * cells, reinterpret_cast<const uint32_t *>(ps + 3 * cells),
-                       fgrid, uint32_t(tm), int64_t(0), (mm && j == a.nv - 1) ? 1 : 0, tb.g, a.v0 + j, ctx->d_flags, 0, (RangeRec *)nullptr);
-            }
-            tiny_used = true;
-            return PassStatus::Done;
-        }
+}
+
+// ---- `col % m`, m <= 4 (the reference's own `group by id % 3`): the register-resident kernel (aggregate_tiny.hip) — no LDS table at all
+bool AggRun::try_register_kernel() {
+    const uint64_t tm = a.key.nops == 1 ? a.key.aux[0].abs_lit : 0;
+    bool tiny = tiny_ok && !jit_whole && ka.direct == 1 && (fast_key == 1 || fast_key == 2) && tm >= 1 && tm <= 4 && (fp == 0 || fp == 1) && !vnull &&
+                subsets_log2 == 0 && key_col >= 0 && a.nv >= 1 && a.nv <= 3 && in->rows >= (int64_t(1) << 20);
+    for (int j = 0; tiny && j < a.nv; ++j) tiny = a.val[j].values != nullptr && (j == a.nv - 1 || !a.need_minmax[j]);
+    // (its tiles are read in 16-byte loads: a column that starts on an odd word — a slice of a borrowed buffer — takes the streaming kernel)
+    tiny = tiny && (reinterpret_cast<uintptr_t>(a.key_src.values) & 15u) == 0;
+    for (int j = 0; tiny && j < a.nv; ++j) tiny = (reinterpret_cast<uintptr_t>(a.val[j].values) & 15u) == 0;
+    if (!tiny) return false;
+    const size_t cells = size_t(fgrid) * size_t(tm), col_words = (cells * 28 + 7) / 8;
+    BufRef partials = dev_alloc(ctx, col_words * 8 * size_t(a.nv) + 64);
+    ka.partials = reinterpret_cast<uint64_t>(partials->ptr);
+    ka.partial_span = uint32_t(tm);
+    const bool mm = a.need_minmax[a.nv - 1] != 0;
+    launch(ctx, "agg_grouped_tiny", pick_tiny_groups_kernel(fp, a.nv, mm, uint32_t(tm), a.val[0].values == a.key_src.values), dim3(fgrid), dim3(AGG_BLOCK), 0, ka, fpred, uint32_t(tm), uint32_t(sw.tiny_unpack_tiles), ctx->d_flags);
+    for (int j = 0; j < a.nv; ++j) {
+        const double *ps = reinterpret_cast<const double *>(partials->ptr) + size_t(j) * col_words;
+        launch(ctx, "agg_fold_partials", agg_fold_partials_kernel, dim3((unsigned(tm) + 15) / 16), dim3(256), 0, ps, ps + cells, ps + 2 * cells, reinterpret_cast<const uint32_t *>(ps + 3 * cells),
+               fgrid, uint32_t(tm), int64_t(0), (mm && j == a.nv - 1) ? 1 : 0, tb.g, a.v0 + j, ctx->d_flags, 0, (RangeRec *)nullptr);
     }
-    const bool jit_chains = !sw.no_agg_jit_chains;
+    tiny_used = true;
+    return true;
+}
+
+// a predicate tree the static kernel would interpret (PRED 5 / 6) over `col % m` keys and one value column: the lean
+// run-time specialised kernel, once it has been compiled — its workgroup tables are folded into the group table here
+// interpreted chain predicates (PRED 3: `id % 10 < 5`, `id * 3 >= K`) take the specialised kernel too: 0.70 -> 0.555 ms per 2x10^8 rows
+bool AggRun::try_specialised_kernel(int v0) {
     BufRef jit_partials;
     uint32_t jit_span = 0;
     int64_t jit_bias = 0;
     // … and so do interpreted chain KEYS (`(id + 1) % 1000`, KEY 3) whatever the predicate: the kernel bakes the whole key program
-    // agg_jit_all = 1: also `col % m` by magic multiply (KEY 2: the literal modulus baked in — `id % 1000` 0.584 -> 0.548 ms, `id % 2000`
-    // 0.643 -> 0.560 per 2x10^8 rows), 2 = every `% m` key (A/B: the headline's power-of-two key 2.53 vs 2.47 ms — within noise, it stays static), 0 = neither
-    const int jit_all = sw.agg_jit_all;
-    const bool jit_try = jit_whole || (has_pred && (fp >= 5 || (fp == 3 && jit_chains))) || (fast_key == 3 && jit_chains) || (jit_all >= 1 && fast_key == 2) || jit_all >= 2;
-    if (jit_try && (fast_key == 1 || fast_key == 2 || fast_key == 3) && ka.direct == 1 && ka.direct_rep == 0 && a.nv == 1 && !vnull && subsets_log2 == 0 &&
+    // … and `col % m` by magic multiply (KEY 2: the literal modulus baked in — `id % 1000` 0.584 -> 0.548 ms, `id % 2000` 0.643 -> 0.560 per
+    // 2x10^8 rows); power-of-two moduli stay static (A/B: the headline's key 2.53 vs 2.47 ms — within noise)
+    const bool jit_try = jit_whole || (has_pred && (fp >= 5 || fp == 3)) || fast_key == 3 || fast_key == 2;
+    if (!(jit_try && (fast_key == 1 || fast_key == 2 || fast_key == 3) && ka.direct == 1 && ka.direct_rep == 0 && a.nv == 1 && !vnull && subsets_log2 == 0 &&
         key_col >= 0 && a.val[0].values &&
         aggregate_tree_specialised(ctx, in, has_pred ? pred : nullptr, pred_nodes, group, group_nodes, plan.val_cols[size_t(v0)], fgrid,
-                                   &jit_partials, &jit_span, &jit_bias)) {
-        const size_t cells = size_t(fgrid) * jit_span;
-        const double *ps = (const double *)jit_partials->ptr;
-        jit_launched = true;
-        launch(ctx, "agg_merge_partials", agg_merge_partials_kernel, dim3((jit_span + 3) / 4), dim3(256), 0, ps, ps + cells, ps + 2 * cells,
-               reinterpret_cast<const uint32_t *>(ps + 3 * cells), fgrid, jit_span, jit_bias, tb.g, a.v0, ctx->d_flags);
-    } else if (jit_whole) {
-        jit_redo = true; // (cannot happen once the dry run said yes — but a static kernel must never run without the predicate)
-        return PassStatus::Abort;
-    } else {
+                                   &jit_partials, &jit_span, &jit_bias)))
+        return false;
+    const size_t cells = size_t(fgrid) * jit_span;
+    const double *ps = (const double *)jit_partials->ptr;
+    jit_launched = true;
+    launch(ctx, "agg_merge_partials", agg_merge_partials_kernel, dim3((jit_span + 3) / 4), dim3(256), 0, ps, ps + cells, ps + 2 * cells,
+           reinterpret_cast<const uint32_t *>(ps + 3 * cells), fgrid, jit_span, jit_bias, tb.g, a.v0, ctx->d_flags);
+    return true;
+}
+
+// the static streaming kernel; a direct-mapped table without validity bitmaps leaves it whole (AggArgs::partials) and is folded behind it
+void AggRun::launch_fast_kernel() {
     FastKernel fk = pick_fast_kernel(fp, fast_key, a.nv, vf64, vnull, subsets_log2 != 0, nomm, share);
     if (!fk) fail(NQE_ERR_NOT_SUPPORTED, "internal: no such variant of the streaming aggregate kernel");
-    // a direct-mapped table without validity bitmaps leaves the kernel whole (AggArgs::partials) and is folded by agg_fold_partials_kernel
     BufRef direct_partials;
     uint32_t pspan = 0;
     size_t pcol_words = 0;
-    if (ka.direct && !vnull && (subsets_log2 == 0 || ka.direct_sub_width) && sw.direct_partials) {
+    if (ka.direct && !vnull && (subsets_log2 == 0 || ka.direct_sub_width)) {
         pspan = ka.direct_sub_width ? uint32_t(ka.lds_cap) : uint32_t(ka.direct == 2 ? range_span : (a.key.op_dtype[a.key.nops - 1] == NQE_INT64 ? 2 * a.key.aux[a.key.nops - 1].abs_lit - 1 : a.key.aux[a.key.nops - 1].abs_lit));
         const size_t cells = size_t(fgrid) * pspan;
         pcol_words = (cells * 28 + 7) / 8;
@@ -1774,25 +1433,27 @@ PassStatus AggRun::tier_streaming(int v0) {
         }
     }
     launch(ctx, "agg_grouped_fast", fk, dim3(fgrid), dim3(AGG_BLOCK), fshmem, ka, fpred, tb.g, ctx->d_flags);
-    if (direct_partials) {
-        const size_t cells = size_t(fgrid) * pspan;
-        for (int j = 0; j < a.nv; ++j) {
-            const double *ps = reinterpret_cast<const double *>(direct_partials->ptr) + size_t(j) * pcol_words;
-            const bool mmj = a.need_minmax[j] != 0 && !(nomm);
-            const int fsub = ka.direct_sub_width ? subsets_log2 : 0;
-            // the subsets' tables cover the key range in order: folded into ONE table of records the range tier's tail ranks and writes (no global
-            // hash table of 16384 slots, no collect / sort / finalize behind a host round trip: ~0.12 ms of a 10^8-row step)
-            // (round 6: so does ONE table of more than 4096 keys — its groups would crowd the first attempt's 8192-slot group table)
-            const bool to_tail = (fsub || pspan > 4096) && V == 1 && sw.range_tier;
-            if (to_tail) range_tab = dev_alloc(ctx, (size_t(pspan) << fsub) * sizeof(RangeRec) + 64);
-            launch(ctx, "agg_fold_partials", agg_fold_partials_kernel, dim3(((pspan << fsub) + 15) / 16), dim3(256), 0, ps, ps + cells, ps + 2 * cells,
-                   reinterpret_cast<const uint32_t *>(ps + 3 * cells), fgrid, pspan, ka.direct_bias, mmj ? 1 : 0, tb.g, a.v0 + j, ctx->d_flags, fsub,
-                   to_tail ? (RangeRec *)range_tab->ptr : (RangeRec *)nullptr);
-            if (to_tail) range_emit(0, 1, pspan << fsub, fsub ? range_span : uint64_t(pspan), fsub ? range_min : -ka.direct_bias); // (one table: slot s holds the key s - direct_bias)
-        }
+    if (direct_partials) fold_direct_partials(direct_partials, pspan, pcol_words);
+}
+
+// the workgroups' direct-mapped tables (fgrid x pspan cells per value column) into the group table — or, where the tables cover a key range in
+// order, into ONE table of records that the range tier's tail ranks and writes
+void AggRun::fold_direct_partials(const BufRef &partials, uint32_t pspan, size_t pcol_words) {
+    const size_t cells = size_t(fgrid) * pspan;
+    for (int j = 0; j < a.nv; ++j) {
+        const double *ps = reinterpret_cast<const double *>(partials->ptr) + size_t(j) * pcol_words;
+        const bool mmj = a.need_minmax[j] != 0 && !(nomm);
+        const int fsub = ka.direct_sub_width ? subsets_log2 : 0;
+        // the subsets' tables cover the key range in order: folded into ONE table of records the range tier's tail ranks and writes (no global
+        // hash table of 16384 slots, no collect / sort / finalize behind a host round trip: ~0.12 ms of a 10^8-row step)
+        // (round 6: so does ONE table of more than 4096 keys — its groups would crowd the first attempt's 8192-slot group table)
+        const bool to_tail = (fsub || pspan > 4096) && V == 1;
+        if (to_tail) range_tab = dev_alloc(ctx, (size_t(pspan) << fsub) * sizeof(RangeRec) + 64);
+        launch(ctx, "agg_fold_partials", agg_fold_partials_kernel, dim3(((pspan << fsub) + 15) / 16), dim3(256), 0, ps, ps + cells, ps + 2 * cells,
+               reinterpret_cast<const uint32_t *>(ps + 3 * cells), fgrid, pspan, ka.direct_bias, mmj ? 1 : 0, tb.g, a.v0 + j, ctx->d_flags, fsub,
+               to_tail ? (RangeRec *)range_tab->ptr : (RangeRec *)nullptr);
+        if (to_tail) range_emit(0, 1, pspan << fsub, fsub ? range_span : uint64_t(pspan), fsub ? range_min : -ka.direct_bias); // (one table: slot s holds the key s - direct_bias)
     }
-    }
-    return PassStatus::Done;
 }
 
 void AggRun::pass_ungrouped(int v0) {
@@ -1886,20 +1547,27 @@ PassStatus AggRun::launch_pass(int v0) {
     return PassStatus::Done;
 }
 
-// what the flags of a finished attempt ask for.  true: the attempt is redone (the members say where)
-bool AggRun::react_to_flags(const int *f, const Collected &pre) {
-    (void)pre;
+// what the flags of a finished attempt ask for.  true: the attempt is redone (the members say where, and the memo where the query shape's
+// next execution starts)
+bool AggRun::react_to_flags(const int *f) {
     if (f[NQE_FLAG_DIV_ZERO]) fail(NQE_ERR_ARROW, "Divide by zero");
     if (f[NQE_FLAG_OVERFLOW]) fail(NQE_ERR_ARROW, "attempt to divide with overflow");
+    if (react_to_key_faults(f)) return true;
+    if (partition_mode ? react_partitioned(f) : react_streaming(f)) return true;
+    if (f[NQE_FLAG_DENSE_OVERFLOW]) { // a sub-partition with more distinct keys than an LDS table: hashed global table instead
+        dense_ok = false;
+        return redo();
+    }
+    return react_table_full(f);
+}
+
+// a key where a tier's promise said none would be: outside [0, m) under the register kernel, outside the range the partitions were cut from
+bool AggRun::react_to_key_faults(const int *f) {
     if (f[NQE_FLAG_OOB] && tiny_used) {
-        // a key outside [0, m) — a negative Int64 — under the tiny-groups kernel: the streaming kernel, now and for this query shape's later executions
+        // a negative Int64 under the tiny-groups kernel: the streaming kernel, now and for this query shape's later executions
         tiny_ok = false;
-        if (hint_key) {
-            if (ctx->agg_key_ranges.size() >= 256) ctx->agg_key_ranges.clear();
-            ctx->agg_key_ranges[hint_key ^ TINY_SALT] = std::make_pair(int64_t(0), uint64_t(0));
-        }
-        flags_reset(ctx);
-        return true;
+        if (hint_key) memo().remember_tiny_rejected();
+        return redo();
     }
     if ((f[NQE_FLAG_OOB] || f[NQE_FLAG_SLAB_OVERFLOW]) && partition_mode && range_part_used) {
         // a key outside the range the partitions were cut from (the sample missed it, the column changed), or key intervals of very
@@ -1911,146 +1579,132 @@ bool AggRun::react_to_flags(const int *f, const Collected &pre) {
         part_span = 0;
         part_range_sampled = false;
         if (!remeasure) range_part_ok = false;
-        if (hint_key && !remeasure) {
-            if (ctx->agg_key_ranges.size() >= 256) ctx->agg_key_ranges.clear();
-            ctx->agg_key_ranges[hint_key ^ PART_RANGE_SALT] = std::make_pair(int64_t(0), uint64_t(0));
-        }
-        flags_reset(ctx);
-        return true;
+        if (hint_key && !remeasure) memo().never_range_partition_again();
+        return redo();
     }
-    if (f[NQE_FLAG_KEY32_OVERFLOW] && partition_mode && !key32_failed) {
+    return false;
+}
+
+// the partitioned ladder: 12-byte -> 16-byte tuples, slabs -> exact sizes, 256 -> PARTS partitions, one -> two levels
+bool AggRun::react_partitioned(const int *f) {
+    if (f[NQE_FLAG_KEY32_OVERFLOW] && !key32_failed) {
         key32_failed = true; // a group key outside int32: the 16-byte tuple form
-        if (hint_key) ctx->agg_hints[hint_key] = uint8_t(0x40 | (slab_parts_log2 < PARTS_LOG2 ? 16 : 1));
-        flags_reset(ctx);
-        return true;
+        if (hint_key) memo().remember_start(slab_start(), true);
+        return redo();
     }
-    if (f[NQE_FLAG_SLAB_OVERFLOW] && partition_mode && !slab_failed) {
+    if (f[NQE_FLAG_SLAB_OVERFLOW] && !slab_failed) {
         slab_failed = true; // a partition outgrew its slab (skewed keys): exact partition sizes instead
-        if (hint_key) ctx->agg_hints[hint_key] = uint8_t(17 | (key32_failed ? 0x40 : 0)); // … and the next execution of this query shape starts there
-        flags_reset(ctx);
-        return true;
+        if (hint_key) memo().remember_start(AggStart::ExactForm, key32_failed); // … and the next execution of this query shape starts there
+        return redo();
     }
-    if (f[NQE_FLAG_NEED_LEVEL2] && partition_mode && !level2 && !slab_failed && slab_parts_log2 < PARTS_LOG2) {
+    if (f[NQE_FLAG_NEED_LEVEL2] && !level2 && !slab_failed && slab_parts_log2 < PARTS_LOG2) {
         slab_parts_log2 = PARTS_LOG2; // a partition outgrew a workgroup table: the full partition count, still in slab form
-        if (hint_key) ctx->agg_hints[hint_key] = uint8_t(1 | (key32_failed ? 0x40 : 0));
-        flags_reset(ctx);
-        return true;
+        if (hint_key) memo().remember_start(AggStart::SlabAllParts, key32_failed);
+        return redo();
     }
-    if (f[NQE_FLAG_NEED_LEVEL2] && partition_mode && !level2) {
+    if (f[NQE_FLAG_NEED_LEVEL2] && !level2) {
         level2 = true; // partitions hold more distinct keys than a workgroup table: one more partitioning level
         cap = std::max<uint32_t>(cap, 1u << 24);
-        flags_reset(ctx);
-        return true;
+        return redo();
     }
-    if (f[NQE_FLAG_NEED_PARTITION] && !partition_mode && range_on) {
+    return false;
+}
+
+// the streaming ladder: a key outside the adopted range -> the exact range; three columns in one pass -> passes of one and two; one
+// workgroup table -> two key subsets or the partitioned path
+bool AggRun::react_streaming(const int *f) {
+    if (f[NQE_FLAG_NEED_PARTITION] && range_on) {
         // a key outside the remembered range (the column's contents changed, or the range came from a sample that missed the
         // column's extremes), or a pass whose table is smaller than the range
         range_on = false;
-        if (hint_key) ctx->agg_key_ranges.erase(hint_key);
+        if (hint_key)
+            if (AggMemo *m = ctx->agg_memo.find(hint_key)) m->forget_key_range();
         flags_reset(ctx);
         if (range_sampled && hint_key) {
             range_sampled = false;
             const auto exact = measure_key_range(); // the exact range: addressed by key - min after all, or remembered as too wide
-            ctx->agg_key_ranges[hint_key] = exact;
-            if (exact.second != 0 && exact.second <= one_table_or_subsets_limit()) {
-                range_on = true;
-                range_min = exact.first;
-                range_span = exact.second;
-            }
+            memo().remember_key_range(exact.first, exact.second);
+            if (exact.second != 0 && exact.second <= one_table_or_subsets_limit()) adopt_key_range(exact.first, exact.second);
         }
         return true;
     }
-    if (f[NQE_FLAG_NEED_PARTITION] && !partition_mode && three) {
+    if (f[NQE_FLAG_NEED_PARTITION] && three) {
         // more groups than the three-column instance's table holds: passes of one and two columns (2048 / 4096 slots) may still do
         three_on = false;
-        if (hint_key) {
-            if (ctx->agg_hints.size() >= 256) ctx->agg_hints.clear();
-            ctx->agg_hints[hint_key] = 0x80;
-        }
-        flags_reset(ctx);
-        return true;
+        if (hint_key) memo().remember_no_three_column_pass();
+        return redo();
     }
-    if (f[NQE_FLAG_NEED_PARTITION] && !partition_mode) {
+    if (f[NQE_FLAG_NEED_PARTITION]) {
         // a workgroup table overflowed: two key subsets, and beyond those hash-partitioned rows
-        bool to_subsets = subsets_ok && subsets_log2 < sw.subsets_max;
-        if (to_subsets && subsets_log2 == 0 && plain_int_key && !sw.no_key_range && V == 1 && sw.direct_subsets && hint_key) {
-            // a plain integer key column: its exact range (one pass, remembered) decides as the key sample does for queries without a predicate —
-            // up to two tables' worth of values: the two subsets address their tables directly; a range the partitioned path's range tier takes:
-            // that tier; anything wider: hashed subsets
-            auto rt = ctx->agg_key_ranges.find(hint_key);
-            if (rt == ctx->agg_key_ranges.end() || range_sampled) {
-                if (ctx->agg_key_ranges.size() >= 256) ctx->agg_key_ranges.clear();
-                ctx->agg_key_ranges[hint_key] = measure_key_range();
-                rt = ctx->agg_key_ranges.find(hint_key);
-                range_sampled = false;
-            }
-            const uint64_t span = rt->second.second;
-            if (span != 0 && span <= direct_one_limit && attempt < 6) { // ONE table addressed by key - min takes it after all (the hashed attempt gave up at three quarters of its slots)
-                range_on = true;
-                range_min = rt->second.first;
-                range_span = span;
-                cap = std::max(cap, std::min(sized_cap, RANK_MAX_CAP << 1));
-                ctx->agg_hints[hint_key] = uint8_t(key32_failed ? 0x40 : 0);
-                flags_reset(ctx);
-                return true;
-            }
-            if (span != 0 && span <= direct_pair_limit) {
-                range_on = true;
-                range_min = rt->second.first;
-                range_span = span;
-            } else if (range_part_ok && sw.range_tier && span != 0 && span < uint64_t(256) * RANGE_TIER_MAX_SLOTS) {
-                to_subsets = false;
-                if (span < (uint64_t(PARTS) << 12)) { // the measured (exact) range is what the range tier cuts its partitions from, in this execution already
-                    part_min = rt->second.first;
-                    part_span = span;
-                    part_range_sampled = false;
-                }
-            }
-        }
+        bool to_subsets = subsets_ok && subsets_log2 < SUBSETS_MAX_LOG2;
+        if (to_subsets && subsets_log2 == 0 && plain_int_key && V == 1 && hint_key && measured_range_picks_the_tier(&to_subsets)) return redo();
         if (to_subsets) {
             ++subsets_log2;
-            cap = std::max(cap, std::min(sized_cap, RANK_MAX_CAP << subsets_log2));
-        } else {
-            subsets_log2 = 0;
-            partition_mode = true;
-            cap = std::max(cap, sized_cap);
-        }
-        if (hint_key) {
-            if (ctx->agg_hints.size() >= 256) ctx->agg_hints.clear();
-            ctx->agg_hints[hint_key] = uint8_t((partition_mode ? (slab_parts_log2 < PARTS_LOG2 ? 16 : 1) : 1 + subsets_log2) | (key32_failed ? 0x40 : 0));
-        }
-        flags_reset(ctx);
+            grow_cap_for_subsets(subsets_log2);
+        } else
+            go_partitioned();
+        if (hint_key) memo().remember_start(partition_mode ? slab_start() : AggStart::TwoSubsets, key32_failed);
+        return redo();
+    }
+    return false;
+}
+
+// a workgroup table of a plain integer key column overflowed: its exact range (one pass, remembered) decides as the key sample does for queries
+// without a predicate — up to one table's worth of values: ONE table addressed by key - min takes it after all (true: redo there; the hashed
+// attempt gave up at three quarters of its slots); up to two tables' worth: the two subsets address their tables directly; a range the
+// partitioned path's range tier takes: that tier (*to_subsets = false); anything wider: hashed subsets
+bool AggRun::measured_range_picks_the_tier(bool *to_subsets) {
+    if (!memo().key_range_known || range_sampled) { // (read whatever NQE_NO_PLAN_HINTS says: this execution's own measurement at the latest)
+        const auto exact = measure_key_range();
+        memo().remember_key_range(exact.first, exact.second);
+        range_sampled = false;
+    }
+    const int64_t min = memo().key_min;
+    const uint64_t span = memo().key_span;
+    if (span != 0 && span <= direct_one_limit && attempt < 6) {
+        adopt_key_range(min, span);
+        grow_cap_for_subsets(1);
+        memo().remember_start(AggStart::Streaming, key32_failed);
         return true;
     }
-    if (f[NQE_FLAG_DENSE_OVERFLOW]) { // a sub-partition with more distinct keys than an LDS table: hashed global table instead
-        dense_ok = false;
-        flags_reset(ctx);
-        return true;
+    if (span != 0 && span <= direct_pair_limit) {
+        adopt_key_range(min, span);
+    } else if (range_part_ok && span != 0 && span < uint64_t(256) * RANGE_TIER_MAX_SLOTS) {
+        *to_subsets = false;
+        if (span < (uint64_t(PARTS) << 12)) { // the measured (exact) range is what the range tier cuts its partitions from, in this execution already
+            part_min = min;
+            part_span = span;
+            part_range_sampled = false;
+        }
     }
-    if (f[NQE_FLAG_TABLE_FULL] && !partition_mode && asked_partition) {
+    return false;
+}
+
+// more groups than the group table holds: the partitioned path, or the next size
+bool AggRun::react_table_full(const int *f) {
+    if (!f[NQE_FLAG_TABLE_FULL]) return false;
+    if (!partition_mode && asked_partition) {
         // More groups than the global table of the streaming tiers holds, while no workgroup's LDS table overflowed: a table of
         // 2^18 .. a few million rows with many groups (every workgroup sees fewer distinct keys than its table holds).  Growing
         // the global table would leave each workgroup folding its LDS table into it through device-scope atomics — as many of
         // them as rows (500 000 rows, 90 000 groups: 1.33 ms in the streaming kernel); the partitioned path has none.
-        subsets_log2 = 0;
-        partition_mode = true;
-        cap = std::max(cap, sized_cap);
-        if (hint_key) {
-            if (ctx->agg_hints.size() >= 256) ctx->agg_hints.clear();
-            ctx->agg_hints[hint_key] = uint8_t((slab_parts_log2 < PARTS_LOG2 ? 16 : 1) | (key32_failed ? 0x40 : 0));
-        }
-        flags_reset(ctx);
-        return true;
+        go_partitioned();
+        if (hint_key) memo().remember_start(slab_start(), key32_failed);
+        return redo();
     }
-    if (f[NQE_FLAG_TABLE_FULL]) {
-        // grow in 64 bits: 2^30 << 3 wraps a uint32_t to 0 (a zero-capacity table, then a spurious overflow error)
-        const uint64_t next = cap < sized_cap ? uint64_t(sized_cap) : uint64_t(cap) << 3;
-        if (cap >= (1u << 31) || attempt > 8) fail(NQE_ERR_OUT_OF_MEMORY, "group table overflow");
-        cap = uint32_t(std::min<uint64_t>(next, uint64_t(1) << 31));
-        flags_reset(ctx);
-        return true;
-    }
-    return false;
+    // grow in 64 bits: 2^30 << 3 wraps a uint32_t to 0 (a zero-capacity table, then a spurious overflow error)
+    const uint64_t next = cap < sized_cap ? uint64_t(sized_cap) : uint64_t(cap) << 3;
+    if (cap >= (1u << 31) || attempt > 8) fail(NQE_ERR_OUT_OF_MEMORY, "group table overflow");
+    cap = uint32_t(std::min<uint64_t>(next, uint64_t(1) << 31));
+    return redo();
+}
+
+// the exact key range [ordlo, ordhi] (sort order) of this query's groups, as a tail measured it: the next execution cuts its key-range
+// partitions from it.  false: too wide for them (or empty) — nothing is remembered
+bool AggRun::remember_group_range(uint64_t ordlo, uint64_t ordhi) {
+    if (!(ordhi >= ordlo && ordhi - ordlo < (uint64_t(PARTS) << 12))) return false;
+    memo().remember_part_range(int64_t(ordlo ^ key_flip), ordhi - ordlo + 1);
+    return true;
 }
 
 // keys_out of a `group by <Utf8 column>`: every tier aggregates the Int64 codes (representative row of each distinct string,
@@ -2082,7 +1736,7 @@ bool AggRun::finish_attempt(AggResult *out) {
     const bool dense_tail = grouped && tb.g.dense_count != nullptr && !ranged.out;
     if (dense_tail) { // group count and key range of the densely written table ride along with the flags (emit: the ranked tail)
         launch(ctx, "agg_dense_key_range", dense_key_range_kernel, dim3(unsigned(std::min<int64_t>(128, (int64_t(tb.g.cap) + 4095) / 4096))), dim3(256), 0, (const uint64_t *)tb.g.keys, tb.g.cap,
-               kinfo.out_dtype == NQE_INT64 ? 0x8000000000000000ull : 0ull, tb.g.dense_count);
+               key_flip, tb.g.dense_count);
         NQE_HIP_CHECK(hipMemcpyAsync(ctx->h_flags + NQE_NUM_FLAGS, tb.g.dense_count, 24, hipMemcpyDeviceToHost, ctx->stream));
     }
     int f[NQE_NUM_FLAGS];
@@ -2101,7 +1755,7 @@ bool AggRun::finish_attempt(AggResult *out) {
         fprintf(stderr, "[nqe] aggregate attempt %d: partition %d subsets_log2 %d cap %u flags need_partition %d slab_overflow %d level2 %d table_full %d dense_overflow %d\n",
                 attempt, int(partition_mode), subsets_log2, cap, f[NQE_FLAG_NEED_PARTITION], f[NQE_FLAG_SLAB_OVERFLOW], f[NQE_FLAG_NEED_LEVEL2],
                 f[NQE_FLAG_TABLE_FULL], f[NQE_FLAG_DENSE_OVERFLOW]);
-    if (react_to_flags(f, pre)) return false;
+    if (react_to_flags(f)) return false;
     if (ranged.out) {
         uint64_t sum3[3];
         std::memcpy(sum3, (const void *)(ctx->h_flags + NQE_NUM_FLAGS), sizeof(sum3));
@@ -2109,27 +1763,14 @@ bool AggRun::finish_attempt(AggResult *out) {
         sum3[1] = range_emit_key_min + ~sum3[1]; // (the tail leaves offsets from key_min: the first one complemented)
         sum3[2] = range_emit_key_min + sum3[2];
         set_group_count(ranged, G);
-        if (hint_key && G > 0) { // the exact range of the groups (the keys come out in order): the next execution cuts its partitions from it
-            const uint64_t flip = kinfo.out_dtype == NQE_INT64 ? 0x8000000000000000ull : 0ull;
-            const uint64_t lo = sum3[1] ^ flip, hi = sum3[2] ^ flip;
-            if (hi >= lo && hi - lo < (uint64_t(PARTS) << 12)) {
-                if (ctx->agg_key_ranges.size() >= 256) ctx->agg_key_ranges.clear();
-                ctx->agg_key_ranges[hint_key ^ PART_RANGE_SALT] = std::make_pair(int64_t(sum3[1]), hi - lo + 1);
-            }
-        }
+        if (hint_key && G > 0) remember_group_range(sum3[1] ^ key_flip, sum3[2] ^ key_flip); // (the keys come out in order)
         keys_to_strings(ranged);
         *out = std::move(ranged);
         return true;
     }
-    if (pre.dense_G > 0 && hint_key && range_part_ok && pre.ordmax >= pre.ordmin && pre.ordmax - pre.ordmin < (uint64_t(PARTS) << 12)) {
-        // the exact key range of this query's groups: the next execution cuts its partitions from it
-        const uint64_t flip = kinfo.out_dtype == NQE_INT64 ? 0x8000000000000000ull : 0ull;
-        if (ctx->agg_key_ranges.size() >= 256) ctx->agg_key_ranges.clear();
-        ctx->agg_key_ranges[hint_key ^ PART_RANGE_SALT] = std::make_pair(int64_t(pre.ordmin ^ flip), pre.ordmax - pre.ordmin + 1);
-        if (sw.debug)
-            fprintf(stderr, "[nqe] aggregate: remembered key range %lld + %llu (hint %llx)\n", (long long)int64_t(pre.ordmin ^ flip), (unsigned long long)(pre.ordmax - pre.ordmin + 1),
-                    (unsigned long long)hint_key);
-    }
+    if (pre.dense_G > 0 && hint_key && range_part_ok && remember_group_range(pre.ordmin, pre.ordmax) && sw.debug)
+        fprintf(stderr, "[nqe] aggregate: remembered key range %lld + %llu (hint %llx)\n", (long long)int64_t(pre.ordmin ^ key_flip), (unsigned long long)(pre.ordmax - pre.ordmin + 1),
+                (unsigned long long)hint_key);
     AggResult res;
     if (ranked.out) {
         set_group_count(ranked, int64_t(uint32_t(f[NQE_FLAG_GROUP_COUNT])));

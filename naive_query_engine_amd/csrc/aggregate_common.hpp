@@ -20,6 +20,9 @@ constexpr int NVMAX = 3;   // … of the one kind of instance that takes three (
 #endif
 constexpr int AGG_U = NQE_AGG_U;   // rows per thread per iteration
 constexpr int AGG_BLOCK = 1024;
+// (settled by the A/B runs of rounds 2-6, as the four further below: DESIGN.md §9 "retired switches")
+constexpr int FLAG_CHECK_MASK = 7;  // a wave of the one-tile streaming loop looks at the overflow flags every 8th iteration (AggArgs::flag_check_mask)
+constexpr int SUBSETS_MAX_LOG2 = 1; // log2 of the key subsets of the streaming tier (AggArgs::subsets_log2: two subsets; four measured slower than partitioning)
 constexpr uint32_t NAN_BIT = 0x80000000u;
 constexpr uint64_t NAN_BIT64 = 0x8000000000000000ull; // the same mark in a 64-bit count (RangeRec)
 
@@ -86,7 +89,7 @@ struct AggArgs {
     int32_t direct;
     int32_t direct_rep; // log2 of the replication of a small direct-mapped table (see the fast kernel): span << direct_rep <= lds_cap
     int64_t direct_bias;
-    uint64_t direct_span; // direct == 2 (a MEASURED key range, nqe_ctx::agg_key_ranges): keys with key + direct_bias >= direct_span are not in it
+    uint64_t direct_span; // direct == 2 (a MEASURED key range, AggMemo::key_min / key_span): keys with key + direct_bias >= direct_span are not in it
     // fast kernel, key subsets: 2^subsets_log2 workgroups share every row range and each keeps only the keys whose hash bits
     // [subset_shift, subset_shift + subsets_log2) name it — 2^subsets_log2 LDS tables' worth of groups without partitioning the rows
     int32_t subsets_log2;
@@ -506,6 +509,10 @@ __device__ __forceinline__ bool row_valid(const ColSrc &c, int64_t row) { return
 // partitioned aggregation (aggregate_partition.hip)
 constexpr int PARTS_LOG2 = 9;
 constexpr int PARTS = 1 << PARTS_LOG2;
+constexpr int SLAB_PARTS_FIRST_LOG2 = 8; // log2 of the first partition count of the hashed slab form (PARTS when one of them outgrows a workgroup table)
+constexpr int SOA_THREADS = 512;         // workgroup size of the two-stream scatter: two per CU (1024 x 1 and 256 x 4 measured slower: profiles/r06/ab_soa_threads.txt)
+constexpr int RANGE_SLOTS_LOG2 = 12;     // log2 of the slots per table the range tier sizes its partition count for (9: 1.11, 10: 1.03, 11: 0.99, 12: 0.97 ms per step at 65536 groups)
+static_assert(SLAB_PARTS_FIRST_LOG2 >= 6 && SLAB_PARTS_FIRST_LOG2 <= PARTS_LOG2, "the first partition count is one the slab kernels have");
 
 struct PartArgs {
     uint32_t *counts;        // [PARTS][nblocks] (count pass out)

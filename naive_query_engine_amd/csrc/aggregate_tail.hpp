@@ -19,6 +19,7 @@ struct FinalizeArgs {
 
 constexpr int DR_BLOCK = 256;
 constexpr int RE_BLOCK = 1024;
+constexpr uint64_t RANGE_EMIT_WIDE_SPAN = uint64_t(1) << 19; // keys per thread of agg_range_emit_kernel: 4 from this many keys of range on, 1 below
 constexpr uint32_t RANK_MAX_CAP = 8192;
 constexpr int RANK_SLOTS = 64;
 constexpr int RANK_WAVES = 16;

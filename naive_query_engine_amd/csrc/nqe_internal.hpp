@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/nqe.h"
+#include "aggregate_memo.hpp"
 
 namespace nqe {
 
@@ -48,27 +49,12 @@ enum { NQE_FLAG_DIV_ZERO = 0, NQE_FLAG_OVERFLOW = 1, NQE_FLAG_TABLE_FULL = 2, NQ
 // group count and key range)
 constexpr int NQE_FLAG_MIRROR_EXTRA = 8;
 
-// Settings of the aggregate operator (aggregate.hip).  Rounds 2-5 read every one of them from the environment for A/B runs; what those
-// runs decided is a constant now (the measurements: profiles/r02 … r05, DESIGN.md §9 "retired switches"), and the forms that lost on
-// every measured shape are gone.  Still read when a context is created: the test hook and the tier trace.  (The switches the tests flip
-// between calls — NQE_NO_PLAN_HINTS, NQE_NO_KEY_SAMPLE, NQE_NO_RANGE_PARTITION, NQE_NO_RANGE_TAIL, NQE_NO_AGG_JIT, NQE_NO_WIDE_DIRECT,
-// NQE_TEST_SLAB_OOM — are read per call where they are used.)
+// Run-time settings of the aggregate operator (aggregate.hip), read when a context is created: a test hook and the tier trace.  What the A/B
+// runs of rounds 2-6 decided is a named constant next to what it sizes (aggregate_common.hpp: FLAG_CHECK_MASK … RANGE_SLOTS_LOG2; aggregate_tail.hpp) or
+// simply the code; DESIGN.md §9 "retired switches" lists the measurements.  (The switches the tests flip between calls — NQE_NO_PLAN_HINTS,
+// NQE_NO_KEY_SAMPLE, NQE_NO_RANGE_PARTITION, NQE_NO_RANGE_TAIL, NQE_NO_AGG_JIT, NQE_NO_WIDE_DIRECT, NQE_TEST_SLAB_OOM — are read per call
+// where they are used.)
 struct AggSwitches {
-    static constexpr bool no_three_column_pass = false; // three value columns without min / max go through ONE pass of the three-column instance
-    static constexpr bool no_key_range = false;         // a plain key column whose measured range fits a workgroup table is addressed by key - min
-    static constexpr int subsets_max = 1;               // log2 of the key subsets of the streaming tier (two subsets; four measured slower than partitioning)
-    static constexpr int slab_parts_first = 8;          // log2 of the first partition count of the hashed slab form
-    static constexpr int flag_check_mask = 7;           // a wave of the one-tile streaming loop looks at the overflow flags every 8th iteration
-    static constexpr bool no_agg_jit_chains = false;    // chain predicates / chain keys take the run-time specialised kernel
-    static constexpr int agg_jit_all = 1;               // `col % m` by magic multiply goes through the specialised kernel (power-of-two moduli stay static)
-    static constexpr bool tiny_groups = true;           // `col % m`, m <= 4: group state in registers (aggregate_tiny.hip)
-    static constexpr bool direct_partials = true;       // direct-mapped workgroup tables leave whole and are folded by a kernel (no device-scope atomics)
-    static constexpr bool range_tier = true;            // key-range partitions: partition count from the range, Q workgroups per partition, transposing tail
-    static constexpr int range_slots_log2 = 12;         // log2 of the slots per table the range tier sizes its partition count for (9: 1.11, 10: 1.03, 11: 0.99, 12: 0.97 ms per step at 65536 groups)
-    static constexpr int soa_threads = 512;             // workgroup size of the two-stream scatter: two per CU (1024 x 1 and 256 x 4 measured slower: profiles/r06/ab_soa_threads.txt)
-    static constexpr bool direct_subsets = true;        // two key subsets over a measured key range address their tables directly
-    static constexpr bool lds_load_limit = true;        // a hashed workgroup table hands over at three quarters of its slots
-    static constexpr int range_emit_items = 0;          // keys per thread of the range tier's tail: by the range (1 below 2^19 keys, else 4)
     int tiny_unpack_tiles = 4096;      // NQE_TINY_UNPACK_TILES: tiles between two unpackings of the register kernel's packed row counters (1..4096; a TEST hook: at 4096 the branch first runs beyond ~2 x 10^9 rows)
     bool debug = false;                // NQE_DEBUG=1: the tier decisions on stderr
     void read_environment();
@@ -100,17 +86,12 @@ struct nqe_ctx {
     };
     std::vector<TimingRec> timings;
 
-    // Grouped aggregates that had to be redone hash-partitioned (more distinct keys than a workgroup's LDS table), remembered by
-    // (key column buffer, rows, key expression): the next execution of the same query over the same table starts partitioned
-    // instead of paying for an abandoned single-pass attempt and its read-back first.  Only a starting point — a partitioned run
-    // is correct for any number of groups, and a single-pass run still falls back when its tables overflow.
     AggSwitches agg_sw;
-    std::map<uint64_t, uint8_t> agg_hints;
-    // … and, by the same key: the value range {min, span} of a plain integer key column (`group by k`: dictionary codes, small ids),
-    // measured by the first execution of the query shape.  A range that fits a workgroup table makes the streaming kernel address
-    // the table by key - min.  The kernel checks every key against the range (the column's contents may have changed under the
-    // entry): a key outside it asks for the other paths, and the entry is dropped.
-    std::map<uint64_t, std::pair<int64_t, uint64_t>> agg_key_ranges;
+    // What grouped aggregates remember per query shape (aggregate_memo.hpp; keyed by a hash of the key column's buffer, the row count, the
+    // key expression, the predicate and the value columns): the tier an earlier execution ended in — the next execution of the same query
+    // over the same table starts there instead of paying for abandoned attempts and their read-backs first — and the value range of a plain
+    // integer key column.  Only starting points: every tier checks what it is given, and the column's contents may have changed under the entry.
+    nqe::AggMemoTable agg_memo;
     // PK-FK joins whose optimistic one-pass probe failed (some foreign key without its primary key), by (build key column, build
     // rows, probe key column, probe rows): HashJoin::execute builds a fresh join table per call (nqe_hash_join_execute), so the
     // verdict has to outlive the table for the next execution of the same join to go straight to the two-pass form
