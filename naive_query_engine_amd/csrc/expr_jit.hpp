@@ -1,6 +1,6 @@
-// expr_jit.hpp — run-time specialisation of the expression machine (included by expr.hip, host code only).
+// expr_jit.hpp — run-time specialisation of the expression machine (host code only; expr.hip includes it, and tools/jit_offline its generators).
 //
-// The stack machine of expr.hip (expr_tree_kernel) interprets an ExProgram per 256-row chunk: operand fetch, stack moves and the
+// The stack machine of expr_kernels.hpp (expr_tree_kernel) interprets an ExProgram per 256-row chunk: operand fetch, stack moves and the
 // (operator, dtype) dispatch are wave-uniform branches around register copies — ≈ 10-14 vector instructions per program step per
 // row against 1-2 for the arithmetic itself, so a tree of more than ~4 operators is issue-bound (an 8-operator chain ran at
 // 2.7 TB/s, `(id % 1000) * 3 + id / 7` at 2.9).  For such trees over large inputs the SAME program is turned into straight-line
@@ -13,7 +13,7 @@
 // a hash of everything baked into the source (steps, dtypes, which columns carry validity, output form, baked divisors); other
 // literals and all pointers are kernel arguments, so `v * 2 > K` does not compile once per K.  Any failure — no libhiprtc, a
 // compile error — marks the entry failed and the interpreter stays: results never depend on the specialisation.
-// Semantics are those of apply_binary / apply_unary / ex_combine (device_utils.hpp, expr.hip), restated in the generated source.
+// Semantics are those of apply_binary / apply_unary / ex_combine (device_utils.hpp, expr_kernels.hpp), restated in the generated source.
 // The two forms are not compiled with the same contraction option (the library: hipcc's default; the generated source:
 // -ffp-contract=off and the pragma) and still agree bit for bit: the interpreter executes every step in its own iteration of a
 // run-time loop, so no multiply ever sits next to the add that could absorb it, and a unary step calls the same sin / cos of the
@@ -32,6 +32,9 @@
 #include <mutex>
 #include <sstream>
 #include <thread>
+
+#include "expr_plan.hpp"
+#include "nqe_internal.hpp"
 
 namespace nqe {
 namespace {
@@ -461,13 +464,16 @@ template <class MakeSource> JitEntry *jit_get(nqe_ctx *ctx, uint64_t key, const 
     return st == 2 ? e : nullptr;
 }
 
+// The two switches every specialised kernel obeys (read per call, not once per process: tests switch them around single calls)
+bool jit_disabled() { return getenv("NQE_NO_JIT") != nullptr; } // diagnostics (A/B)
+int64_t jit_min_rows() {                                        // inputs below this many rows are interpreted
+    const char *mr = getenv("NQE_JIT_MIN_ROWS");
+    return mr ? atoll(mr) : (int64_t(1) << 22);
+}
+
 // Runs P specialised when that pays and the kernel is ready.  Returns false when the caller should interpret.
 bool jit_expr_tree(nqe_ctx *ctx, const ExProgram &P, bool nulls, int64_t rows, uint64_t *ow, uint64_t *ob, uint64_t *ov) {
-    // (read per call, not once per process: tests switch them around single calls)
-    const bool off = getenv("NQE_NO_JIT") != nullptr; // diagnostics (A/B)
-    const char *mr = getenv("NQE_JIT_MIN_ROWS");
-    const int64_t min_rows = mr ? atoll(mr) : (int64_t(1) << 22);
-    if (off || P.n < 3 || rows < min_rows) return false; // one or two steps run at the memory system's rate interpreted
+    if (jit_disabled() || P.n < 3 || rows < jit_min_rows()) return false; // one or two steps run at the memory system's rate interpreted
     const bool bool_out = ob != nullptr;
     JitEntry *e = jit_get(ctx, jit_hash(P, nulls, bool_out), "nqe_jit_expr", [&] { return gen_source(P, nulls, bool_out); });
     if (!e) return false;

@@ -1,8 +1,8 @@
 // Offline check of the run-time specialised kernels' GENERATORS (csrc/expr_jit.hpp) — no GPU needed: builds representative programs
 // by hand, prints the generated source of each kernel family between "//==== <name>" markers; tools/jit_offline/run.sh compiles
 // every one with hipRTC exactly as the library does (rtc_compile.cpp) and reports registers / spills from the code objects.
-// Includes expr.hip wholesale (the generators live in its anonymous namespace) and links libnqe_hip.so for the host symbols.
-#include "../../naive_query_engine_amd/csrc/expr.hip"
+// Includes the generators' header (expr_jit.hpp, with the program types of expr_plan.hpp) and links libnqe_hip.so for the host symbols.
+#include "../../naive_query_engine_amd/csrc/expr_jit.hpp"
 #include <cstdio>
 using namespace nqe;
 
