@@ -1076,9 +1076,9 @@ PassStatus AggRun::tier_slab() {
     // their tuples hold key - range_min, which fits 32 bits whatever the keys' magnitude
     const bool range_part = a.nv == 1 && dense && range_part_ok && part_span != 0 && part_span <= (uint64_t(PARTS) << 12);
     const bool k32 = a.nv == 1 && (!key32_failed || range_part);
-    const int rpt = k32 ? slab_scatter_soa_rows_per_thread() : slab_scatter_rows_per_thread(fp, fast_key, a.nv);
+    const int rpt = k32 ? SOA_RPT : slab_scatter_rows_per_thread(fp, fast_key, a.nv);
     // the two-stream form runs 512-thread workgroups, two per CU: their barrier phases overlap
-    const int sc_threads = k32 ? SOA_THREADS : AGG_BLOCK, sc_per_cu = k32 ? 1024 / SOA_THREADS : slab_scatter_wg_per_cu();
+    const int sc_threads = k32 ? SOA_THREADS : AGG_BLOCK, sc_per_cu = k32 ? 1024 / SOA_THREADS : SLAB_WG_PER_CU;
     const int64_t tile_rows = int64_t(sc_threads) * rpt;
     int W = int(std::min<int64_t>(int64_t(ctx->num_cus) * sc_per_cu, (in->rows + tile_rows - 1) / tile_rows));
     int64_t chunk = ((in->rows + W - 1) / W + tile_rows - 1) / tile_rows * tile_rows;
@@ -1125,11 +1125,8 @@ PassStatus AggRun::tier_slab() {
     sl.parts_log2 = sparts_log2;
     sl.range_min = part_min;
     sl.range_span = range_part ? part_span : 0;
-    // (K32: the SoA scatter — stage and carry buffers of 12 bytes per tuple, five counters per partition, the block owner map)
-    const size_t sc_carry = size_t(sparts) << (sparts_log2 <= 8 ? 4 : 3);
-    const size_t sc_shmem = k32 ? (size_t(tile_rows) + sc_carry) * 12 + size_t(sparts) * 20 + (size_t(tile_rows) / 8 + size_t(sparts)) * 2 + 16 : size_t(tile_rows) * 8 * tw + size_t(PARTS) * 12;
-    launch(ctx, "agg_partition_scatter", pick_slab_scatter_kernel(fp, fast_key, a.nv, k32, sc_threads), dim3(W), dim3(sc_threads), sc_shmem, ka, fpred, sl,
-           ctx->d_flags);
+    const size_t sc_shmem = k32 ? SoaScatterLayout(int(tile_rows), sparts_log2).bytes() : SlabScatterLayout(int(tile_rows), a.nv, PARTS).bytes();
+    launch(ctx, "agg_partition_scatter", pick_slab_scatter_kernel(fp, fast_key, a.nv, k32), dim3(W), dim3(sc_threads), sc_shmem, ka, fpred, sl, ctx->d_flags);
     AggArgs sa = ka;
     size_t sshmem = shmem;
     int sblocks = blocks_per_cu;
@@ -1140,7 +1137,7 @@ PassStatus AggRun::tier_slab() {
         return PassStatus::Done;
     }
     if (range_part) { // tables addressed by key - base: 28 bytes per key of the partition's interval
-        const size_t dshmem = size_t(28) * size_t(rslots) + 16;
+        const size_t dshmem = RangeTableLayout(uint32_t(rslots)).bytes();
         const int dblocks = int(std::max<size_t>(1, std::min<size_t>(4, (size_t(144) << 10) / dshmem)));
         launch(ctx, "agg_segments_direct", pick_slab_segments_direct_kernel(vf64), dim3(std::min(used_parts, ctx->num_cus * dblocks)), dim3(AGG_BLOCK), dshmem, sa,
                sl, tb.g, ctx->d_flags);
@@ -1168,7 +1165,7 @@ int AggRun::slab_partitions_log2(bool range_part, bool range_tier) const {
 // writes the groups.  Nothing here waits for the device: the group count travels back with the flags (finish_attempt).
 void AggRun::range_tail(const AggArgs &sa, const SlabArgs &sl, uint32_t rslots) {
     const int parts = 1 << sl.parts_log2;
-    const size_t dshmem = size_t(28) * size_t(rslots) + 16;
+    const size_t dshmem = RangeTableLayout(rslots).bytes();
     const int per_cu = dshmem <= (size_t(72) << 10) ? 2 : 1; // 1024-thread workgroups: two per CU when their tables fit side by side
     const int Q = std::max(1, std::min(ctx->num_cus * per_cu / parts, sl.W));
     range_tab = dev_alloc(ctx, size_t(parts) * size_t(Q) * size_t(rslots) * sizeof(RangeRec) + 64);
@@ -1225,7 +1222,7 @@ void AggRun::tier_exact() {
     pa.counts = (uint32_t *)counts->ptr;
     pa.offsets = (const uint64_t *)offs->ptr;
     pa.chunk = chunk;
-    launch(ctx, "agg_partition_count", pick_part_kernel(fp, fast_key, a.nv, false), dim3(nblk), dim3(AGG_BLOCK), 0, ka, fpred, pa);
+    launch(ctx, "agg_partition_count", pick_part_kernel(fp, fast_key), dim3(nblk), dim3(AGG_BLOCK), 0, ka, fpred, pa);
     exclusive_scan_u32_to_u64(ctx, (const uint32_t *)counts->ptr, (uint64_t *)offs->ptr, ncnt);
     const int64_t R = int64_t(read_scalar(ctx, (const uint64_t *)offs->ptr + ncnt));
     if (R > 0) {
@@ -1234,10 +1231,9 @@ void AggRun::tier_exact() {
         pa.out_key = (uint64_t *)okey->ptr;
         pa.out_val[0] = (uint64_t *)ov0->ptr;
         pa.out_val[1] = ov1 ? (uint64_t *)ov1->ptr : nullptr;
-        const size_t sc_rows = size_t(AGG_BLOCK) * (a.nv == 1 ? 8 : 4);
-        const size_t sc_shmem = sc_rows * 8 * size_t(1 + a.nv) + size_t(PARTS) * (8 + 4 + 4);
-        launch(ctx, "agg_partition_scatter", pick_scatter_kernel(fp, fast_key, a.nv), dim3(nblk), dim3(AGG_BLOCK), sc_shmem, ka, fpred,
-               pa);
+        const int sc_rows = AGG_BLOCK * ExactScatterLayout::rows_per_thread(a.nv);
+        launch(ctx, "agg_partition_scatter", pick_scatter_kernel(fp, fast_key, a.nv), dim3(nblk), dim3(AGG_BLOCK), ExactScatterLayout(sc_rows, a.nv, PARTS).bytes(), ka,
+               fpred, pa);
         AggArgs sa = ka;
         size_t sshmem = shmem;
         int sblocks = blocks_per_cu;
@@ -1254,7 +1250,7 @@ void AggRun::tier_exact() {
             if (a.nv > 1) v12 = dev_alloc(ctx, size_t(R) * 8 + 8);
             BufRef suboff = dev_alloc(ctx, size_t(PARTS) * SUB * 8 + 16);
             auto subk = pick_subpartition_kernel(a.nv);
-            launch(ctx, "agg_subpartition", subk, dim3(std::min(PARTS, ctx->num_cus)), dim3(AGG_BLOCK), sc_rows * 8 * size_t(1 + a.nv),
+            launch(ctx, "agg_subpartition", subk, dim3(std::min(PARTS, ctx->num_cus)), dim3(AGG_BLOCK), SubStageLayout(sc_rows, a.nv).bytes(),
                    (const uint64_t *)offs->ptr, int64_t(nblk), (const uint64_t *)okey->ptr, (const uint64_t *)ov0->ptr,
                    ov1 ? (const uint64_t *)ov1->ptr : (const uint64_t *)nullptr, (uint64_t *)k2->ptr, (uint64_t *)v02->ptr,
                    v12 ? (uint64_t *)v12->ptr : (uint64_t *)nullptr, (uint64_t *)suboff->ptr);

@@ -5,6 +5,7 @@
 #pragma once
 #include <cfloat>
 
+#include "aggregate_partition_layout.hpp"
 #include "device_utils.hpp"
 #include "nqe_internal.hpp"
 
@@ -512,6 +513,16 @@ constexpr int PARTS = 1 << PARTS_LOG2;
 constexpr int SLAB_PARTS_FIRST_LOG2 = 8; // log2 of the first partition count of the hashed slab form (PARTS when one of them outgrows a workgroup table)
 constexpr int SOA_THREADS = 512;         // workgroup size of the two-stream scatter: two per CU (1024 x 1 and 256 x 4 measured slower: profiles/r06/ab_soa_threads.txt)
 constexpr int RANGE_SLOTS_LOG2 = 12;     // log2 of the slots per table the range tier sizes its partition count for (9: 1.11, 10: 1.03, 11: 0.99, 12: 0.97 ms per step at 65536 groups)
+// (settled A/B knobs of the slab form, like the ones above)
+constexpr int SLAB_WG_PER_CU = 1;        // scatter workgroups per CU of the 16/24-byte-tuple scatter: 2 = half tiles (4 rows per thread, 70 KB of LDS each) whose barrier phases
+                                         // overlap — measured slower: kernels 1.06 -> 1.12 ms at 65536 groups, 1.17 -> 1.29 at 2^20 (shorter runs per partition per tile)
+constexpr int SLAB_KEYMOD_RPT = 8;       // rows per thread of the `col % m` key variants: 8 spill 14-16 VGPRs and are still faster than 4 without (scatter 0.85 vs 0.93 ms)
+constexpr int SOA_RPT = 4;               // rows per thread per tile of the two-stream scatter (every store is a whole block: the tile size no longer decides the store shape)
+constexpr int DIRECT_SU = 4;             // tuples per lane per step of the key-range second-stage kernels (8 measured the same: 0.32-0.33 ms per 10^8 tuples either way —
+                                         // the kernels are bound by their LDS atomics, not by loads in flight)
+// rows per thread per tile of the 16/24-byte-tuple scatter: 8 where the registers allow two tiles in flight (one value column, predicate on
+// the key column or none, a built-in key), else 4
+constexpr int slab_scatter_rows_per_thread(int pred, int key, int nv) { return (nv == 1 && pred <= 1 && (key == 0 || (SLAB_KEYMOD_RPT == 8 && key != 3))) ? 8 : 4; }
 static_assert(SLAB_PARTS_FIRST_LOG2 >= 6 && SLAB_PARTS_FIRST_LOG2 <= PARTS_LOG2, "the first partition count is one the slab kernels have");
 
 struct PartArgs {
@@ -560,17 +571,14 @@ using FastKernel = void (*)(AggArgs, FastPred, GroupTable, int *);
 FastKernel pick_fast_kernel(int pred, int key, int nv, bool vf64, bool vnull, bool sub = false, bool nomm = false, bool share = false);
 using PartKernel = void (*)(AggArgs, FastPred, PartArgs);
 PartKernel pick_scatter_kernel(int pred, int key, int nv);
-PartKernel pick_part_kernel(int pred, int key, int nv, bool scatter);
+PartKernel pick_part_kernel(int pred, int key); // the count pass
 using SubpartitionKernel = void (*)(const uint64_t *, int64_t, const uint64_t *, const uint64_t *, const uint64_t *, uint64_t *, uint64_t *, uint64_t *, uint64_t *);
 SubpartitionKernel pick_subpartition_kernel(int nv);
 using SegmentsKernel = void (*)(AggArgs, const uint64_t *, int64_t, int, int, int, const uint64_t *, const uint64_t *, const uint64_t *, GroupTable, int *);
 SegmentsKernel pick_segments_kernel(int nv, bool vf64);
 using SlabScatterKernel = void (*)(AggArgs, FastPred, SlabArgs, int *);
 // k32 (one value column): 12-byte tuples {int32 key, value} — the scatter raises NQE_FLAG_KEY32_OVERFLOW on a key outside int32
-SlabScatterKernel pick_slab_scatter_kernel(int pred, int key, int nv, bool k32 = false, int soa_threads = 1024); // soa_threads: workgroup size of the K32 (two-stream) form
-int slab_scatter_rows_per_thread(int pred, int key, int nv);
-int slab_scatter_soa_rows_per_thread(); // the K32 (SoA, whole-block) scatter
-int slab_scatter_wg_per_cu();
+SlabScatterKernel pick_slab_scatter_kernel(int pred, int key, int nv, bool k32 = false);
 // key-range partitions: partition of d = key - range_min, and the scramble of the slot that rebuilds the key's low bits from (partition, slot)
 __device__ __forceinline__ uint32_t range_scramble(uint32_t hi, int parts_log2) { return uint32_t((uint64_t(hi * 0x9E3779B1u) << parts_log2) >> 32); } // (parts_log2 == 0: 0)
 __device__ __forceinline__ uint32_t range_partition(uint64_t d, int parts_log2) {
