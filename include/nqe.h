@@ -532,6 +532,31 @@ nqe_status nqe_aggregate_merge_packed(nqe_ctx *ctx, const void *gathered_device,
                                       int32_t grouped, int32_t key_dtype, const nqe_aggregate *aggs, int32_t num_aggs,
                                       nqe_table **out, nqe_table **keys_out);
 
+/* ------------------------------------------------------------------ hash aggregate on several keys
+ * GROUP BY honouring EVERY group expression — quirk Q20: the reference's planner builds `group by a, b` plans and its logical
+ * Aggregate's schema is "group fields, then aggregate fields" (logical_plan/dataframe.rs:58-67, Q13), but
+ * PhysicalAggregatePlan::execute reads group_expr[0] alone (aggregate/mod.rs:146, Q8, which nqe_aggregate_execute reproduces).
+ * Key i is the post-order node range [group_offsets[i], group_offsets[i+1]) of `group_nodes` (nqe_projection_execute's
+ * convention).  Rows group by the whole tuple (key_0, ..., key_{k-1}): two tuples are equal iff every integer key is equal as a
+ * 64-bit word and every Utf8 key byte for byte; a row is dropped if ANY of its keys is NULL (aggregate/mod.rs:64 at every
+ * position); `pred` means what it means in nqe_aggregate_execute (Q4 included); a tuple whose rows are all rejected or dropped
+ * gives no output row.
+ * Output: ONE table of the k key columns in key order (the key's dtype, no validity buffer, null_count 0) followed by one column
+ * per aggregate with the dtypes and Q10 semantics of nqe_aggregate_execute.  Rows are sorted ascending by the key tuple, key 0
+ * most significant — Int64 signed, UInt64 unsigned, Utf8 in byte order: nqe_sort_execute's order with default options — so the
+ * output is deterministic; zero groups give a 0-row table with every column.  With num_keys == 1 and an integer key the
+ * aggregate columns are those of nqe_aggregate_execute (counts, min, max bit for bit; sums and averages to 1e-9 relative) and the
+ * key column is its keys_out.  Nothing is kept between calls.
+ * Errors, all before any launch or allocation: num_keys <= 0 NQE_ERR_PLAN (the un-grouped form stays with
+ * nqe_aggregate_execute); num_keys > NQE_MAX_GROUP_KEYS NQE_ERR_NOT_SUPPORTED; offsets that do not ascend or a NULL `out`
+ * NQE_ERR_INVALID_ARGUMENT; a key whose dtype is not Int64, UInt64 or Utf8, or a Utf8 key that is not a bare column,
+ * NQE_ERR_NOT_SUPPORTED (aggregate/mod.rs:217), also at 0 rows; everything about `pred` and `aggs` as nqe_aggregate_execute
+ * reports it.  A key expression that faults (division by zero) reports what nqe_expr_evaluate reports. */
+#define NQE_MAX_GROUP_KEYS 8
+nqe_status nqe_group_aggregate_execute(nqe_ctx *ctx, const nqe_table *in, const nqe_expr_node *pred, int32_t pred_nodes,
+                                       const nqe_expr_node *group_nodes, const int32_t *group_offsets, int32_t num_keys,
+                                       const nqe_aggregate *aggs, int32_t num_aggs, nqe_table **out);
+
 /* ------------------------------------------------------------------ hash join
  * HashJoin::execute = build() + probe() (hash_join.rs:124-254, :280-284) for one left
  * (build) batch and one right (probe) batch: inner equi-join on

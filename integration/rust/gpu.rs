@@ -106,6 +106,8 @@ extern "C" {
                                         nodes: *const NqeExprNode, expr_offsets: *const i32, num_exprs: i32, out: *mut *mut NqeTable) -> i32;
     fn nqe_aggregate_execute(ctx: *mut NqeCtx, input: *const NqeTable, pred: *const NqeExprNode, pred_nodes: i32, group: *const NqeExprNode,
                              group_nodes: i32, aggs: *const NqeAggregate, num_aggs: i32, out: *mut *mut NqeTable, keys_out: *mut *mut NqeTable) -> i32;
+    fn nqe_group_aggregate_execute(ctx: *mut NqeCtx, input: *const NqeTable, pred: *const NqeExprNode, pred_nodes: i32, group_nodes: *const NqeExprNode,
+                                   group_offsets: *const i32, num_keys: i32, aggs: *const NqeAggregate, num_aggs: i32, out: *mut *mut NqeTable) -> i32;
     fn nqe_hash_join_build(ctx: *mut NqeCtx, left: *const NqeTable, left_key: i32, out: *mut *mut NqeJoinTable) -> i32;
     fn nqe_hash_join_probe(ctx: *mut NqeCtx, build: *const NqeJoinTable, right: *const NqeTable, right_key: i32, out: *mut *mut NqeTable) -> i32;
     fn nqe_join_table_release(jt: *mut NqeJoinTable) -> i32;
@@ -531,6 +533,60 @@ impl GpuExec for GpuAggregatePlan {
 }
 impl PhysicalPlan for GpuAggregatePlan {
     fn schema(&self) -> &NaiveSchema { self.input.schema() } // the INPUT schema, as the reference returns (aggregate/mod.rs:44, quirk Q8)
+    fn children(&self) -> Result<Vec<PhysicalPlanRef>> { Ok(vec![self.input.clone()]) }
+    fn execute(&self) -> Result<Vec<RecordBatch>> { self.ctx.download_all(&self.execute_device()?, &self.out_schema) }
+    fn as_any(&self) -> &dyn Any { self }
+    fn as_gpu(&self) -> Option<&dyn GpuExec> { Some(self) }
+}
+
+/// GROUP BY honouring every group expression (quirk Q20: the reference's planner builds `group by a, b` plans and
+/// PhysicalAggregatePlan::execute reads group_expr[0] alone, aggregate/mod.rs:146): the input batches are concatenated and ONE batch
+/// leaves, the key columns in key order followed by one column per aggregate, sorted ascending by the key tuple; a row with a NULL in
+/// any key is dropped.  `rewrite` keeps mapping PhysicalAggregatePlan to GpuAggregatePlan (Q8): a front end that wants every key
+/// honoured creates this operator directly, with `filter` = the predicate of a SelectionPlan below it.
+#[derive(Debug)]
+pub struct GpuGroupedAggregatePlan {
+    input: PhysicalPlanRef, group_expr: Vec<PhysicalExprRef>, aggs: Vec<(AggregateFunc, ColumnExpr)>, filter: Option<PhysicalExprRef>,
+    out_schema: NaiveSchema, ctx: Arc<GpuCtx>,
+}
+impl GpuGroupedAggregatePlan {
+    /// `out_schema`: the group fields, then the aggregates' `data_field`s (the logical Aggregate's schema, dataframe.rs:58-67)
+    pub fn create(ctx: Arc<GpuCtx>, input: PhysicalPlanRef, group_expr: Vec<PhysicalExprRef>, aggs: Vec<(AggregateFunc, ColumnExpr)>,
+                  filter: Option<PhysicalExprRef>, out_schema: NaiveSchema) -> Result<PhysicalPlanRef> {
+        if group_expr.is_empty() { return Err(ErrorCode::PlanError("GpuGroupedAggregatePlan: the list of group expressions is empty".to_string())); }
+        Ok(Arc::new(Self { input, group_expr, aggs, filter, out_schema, ctx }))
+    }
+}
+impl GpuExec for GpuGroupedAggregatePlan {
+    fn execute_device(&self) -> Result<Vec<GpuBatch>> {
+        let in_schema = self.input.schema();
+        let mut batches = child_device(&self.ctx, &self.input)?;
+        let mut filter = self.filter.clone();
+        if batches.len() > 1 && filter.is_some() {
+            // the fused predicate is per row; over several batches the reference's selection is not (Q3): run it unfused
+            let sel = GpuSelectionPlan { input: self.input.clone(), expr: filter.take().unwrap(), project: None, ctx: self.ctx.clone() };
+            batches = sel.select(&batches)?;
+        }
+        let single = self.ctx.concat(&batches)?;
+        let (mut pred, mut group, mut keep) = (vec![], vec![], vec![]);
+        if let Some(f) = &filter { flatten(f, in_schema, &mut pred, &mut keep)?; }
+        let mut offsets: Vec<i32> = vec![0];
+        for g in &self.group_expr { // every group expression, back to back (nqe_projection_execute's convention)
+            flatten(g, in_schema, &mut group, &mut keep)?;
+            offsets.push(group.len() as i32);
+        }
+        let aggs = self.aggs.iter().map(|(f, c)| Ok(NqeAggregate { func: f.clone() as i32, column: resolve(c, in_schema)? })).collect::<Result<Vec<_>>>()?;
+        let mut out = std::ptr::null_mut();
+        let st = unsafe {
+            nqe_group_aggregate_execute(self.ctx.0, single.table.0, pred.as_ptr(), pred.len() as i32, group.as_ptr(), offsets.as_ptr(),
+                                        self.group_expr.len() as i32, aggs.as_ptr(), aggs.len() as i32, &mut out)
+        };
+        self.ctx.check(st)?;
+        Ok(vec![GpuBatch::wrap(out)]) // one row per key tuple, sorted by the tuple
+    }
+}
+impl PhysicalPlan for GpuGroupedAggregatePlan {
+    fn schema(&self) -> &NaiveSchema { &self.out_schema } // group fields, then aggregate fields (Q13's logical order)
     fn children(&self) -> Result<Vec<PhysicalPlanRef>> { Ok(vec![self.input.clone()]) }
     fn execute(&self) -> Result<Vec<RecordBatch>> { self.ctx.download_all(&self.execute_device()?, &self.out_schema) }
     fn as_any(&self) -> &dyn Any { self }

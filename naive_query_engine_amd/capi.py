@@ -27,7 +27,7 @@ SYMBOLS = [
     "nqe_table_download_column", "nqe_table_project", "nqe_table_slice", "nqe_table_concat", "nqe_table_pack_words",
     "nqe_table_unpack_words", "nqe_csv_infer_schema", "nqe_csv_read", "nqe_expr_evaluate",
     "nqe_filter", "nqe_selection_execute", "nqe_projection_execute", "nqe_selection_projection_execute",
-    "nqe_aggregate_execute", "nqe_aggregate_partial", "nqe_aggregate_merge", "nqe_aggregate_merge_packed", "nqe_hash_join_execute",
+    "nqe_aggregate_execute", "nqe_aggregate_partial", "nqe_aggregate_merge", "nqe_aggregate_merge_packed", "nqe_group_aggregate_execute", "nqe_hash_join_execute",
     "nqe_hash_join_build", "nqe_hash_join_probe", "nqe_join_table_release", "nqe_join_marks_create", "nqe_join_marks_release",
     "nqe_hash_join_probe_outer", "nqe_hash_join_unmatched_build", "nqe_cross_join_execute", "nqe_nested_loop_join_execute", "nqe_sort_execute", "nqe_take", "nqe_synth_fill",
     "nqe_device_alloc", "nqe_device_free",
@@ -132,6 +132,7 @@ def lib():
         "nqe_aggregate_partial": (i32, [vp, vp, nodes, i32, nodes, i32, C.POINTER(NqeAggregate), i32, pvp, pvp]),
         "nqe_aggregate_merge": (i32, [vp, pvp, pvp, i32, C.POINTER(NqeAggregate), i32, pvp, pvp]),
         "nqe_aggregate_merge_packed": (i32, [vp, vp, i32, i64, i32, i32, C.POINTER(NqeAggregate), i32, pvp, pvp]),
+        "nqe_group_aggregate_execute": (i32, [vp, vp, nodes, i32, nodes, C.POINTER(i32), i32, C.POINTER(NqeAggregate), i32, pvp]),
         "nqe_hash_join_execute": (i32, [vp, vp, vp, i32, i32, pvp]),
         "nqe_hash_join_build": (i32, [vp, vp, i32, pvp]),
         "nqe_hash_join_probe": (i32, [vp, vp, vp, i32, pvp]),
@@ -171,6 +172,7 @@ def lib():
 
 
 TABLE_IMMUTABLE = 1  # NQE_TABLE_IMMUTABLE
+MAX_GROUP_KEYS = 8   # NQE_MAX_GROUP_KEYS
 JOIN_KEEP_PROBE = 1  # NQE_JOIN_KEEP_PROBE
 
 
@@ -355,6 +357,15 @@ class Context:
         if with_keys:
             return out, (Table(self, k) if k.value else None)
         return out
+
+    def group_aggregate(self, table: "Table", keys, aggs, pred_nodes=None) -> "Table":
+        """GROUP BY on every key of `keys` (quirk Q20; each key a flattened expression): one table of the key columns in key order
+        followed by one column per aggregate, sorted ascending by the key tuple; a row with a NULL in any key is dropped"""
+        parr, pn = self._nodes(pred_nodes)
+        garr, offs, nk = self._flat([list(k) for k in keys])  # (no keys: one empty node, offsets [0], num_keys 0 — NQE_ERR_PLAN)
+        h = C.c_void_p()
+        self.check(lib().nqe_group_aggregate_execute(self.handle, table.handle, parr, pn, garr, offs, nk, self._aggs(aggs), len(aggs), C.byref(h)))
+        return Table(self, h)
 
     def aggregate_partial(self, table: "Table", aggs, group_nodes=None, pred_nodes=None):
         parr, pn = self._nodes(pred_nodes)

@@ -1809,6 +1809,9 @@ AggResult run_aggregate(nqe_ctx *ctx, const nqe_table *in, const nqe_expr_node *
 
 } // namespace
 
+// the checks of the aggregate list alone, for a caller that must refuse a bad list before it launches anything (group_keys.hip)
+void check_aggregates(const nqe_table *in, const nqe_aggregate *aggs, int naggs) { (void)plan_aggs(in, aggs, naggs); }
+
 } // namespace nqe
 
 using namespace nqe;

@@ -334,6 +334,8 @@ bool aggregate_tree_specialised(nqe_ctx *ctx, const nqe_table *in, const nqe_exp
                                 int val_col, int grid, BufRef *partials, uint32_t *span_out, int64_t *bias_out, bool dry_run = false);
 // evaluates `e` over `in` and compacts the result in the same pass
 DevColumn compact_simple_expr(nqe_ctx *ctx, const nqe_table *in, const SimpleExpr &e, const KeepMask &km);
+// aggregate.hip: fails as nqe_aggregate_execute would for this aggregate list (count, function, column index, column type); launches nothing
+void check_aggregates(const nqe_table *in, const nqe_aggregate *aggs, int naggs);
 
 } // namespace nqe
 

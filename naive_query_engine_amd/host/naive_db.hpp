@@ -583,6 +583,86 @@ struct PhysicalAggregatePlan : PhysicalPlan { // aggregate/mod.rs:31-223
     }
 };
 
+// ---------------------------------------------------------------- group by on several keys (no reference file: aggregate/mod.rs:146 reads group_expr[0] alone)
+// Quirk Q20: GROUP BY honouring EVERY group expression; PhysicalAggregatePlan above keeps Q8.  The input batches are concatenated and ONE
+// batch leaves: the key columns in key order, then one column per aggregate (Q13's logical order), sorted ascending by the key tuple.  A
+// row with a NULL in any key is dropped.  A key field takes the column's field name for a bare ColumnExpr and `group_<i>` otherwise.
+// Nothing is kept between execute() calls.
+struct GroupedAggregatePlan : PhysicalPlan {
+    std::vector<PhysicalExprRef> group_expr;
+    std::vector<std::shared_ptr<AggregateOperator>> aggr_ops; // shared so that the rewrite pass can re-parent them
+    PhysicalPlanRef input;
+    NaiveSchema schema_; // the OUTPUT schema: group fields, then aggregate fields
+    static std::shared_ptr<GroupedAggregatePlan> create_shared(std::vector<PhysicalExprRef> group_expr, std::vector<std::shared_ptr<AggregateOperator>> aggr_ops, PhysicalPlanRef input) {
+        if (group_expr.empty()) throw ErrorCode(ErrorCode::PlanError, "GroupedAggregatePlan: the list of group expressions is empty (the un-grouped form is PhysicalAggregatePlan's)");
+        auto p = std::make_shared<GroupedAggregatePlan>();
+        p->group_expr = std::move(group_expr);
+        p->aggr_ops = std::move(aggr_ops);
+        p->input = std::move(input);
+        p->schema_ = p->output_schema(p->input->schema(), nullptr);
+        return p;
+    }
+    static PhysicalPlanRef create(std::vector<PhysicalExprRef> group_expr, std::vector<std::unique_ptr<AggregateOperator>> aggr_ops, PhysicalPlanRef input) {
+        std::vector<std::shared_ptr<AggregateOperator>> ops;
+        for (auto &op : aggr_ops) ops.push_back(std::move(op));
+        return create_shared(std::move(group_expr), std::move(ops), std::move(input));
+    }
+    // `out`: the executed table, whose key columns carry the real types; before execution the first referenced column's type stands in
+    // (integer arithmetic keeps its operands' type)
+    NaiveSchema output_schema(const NaiveSchema &below, const nqe_table *out) const {
+        std::vector<NaiveField> fields;
+        for (size_t i = 0; i < group_expr.size(); ++i) {
+            std::vector<nqe_expr_node> nodes;
+            group_expr[i]->flatten(below, nodes);
+            DataType dt = DataType::Int64;
+            for (auto &n : nodes)
+                if (n.kind == NQE_EXPR_COLUMN) { dt = below.field(size_t(n.column)).data_type; break; }
+            if (out) {
+                nqe_column info;
+                if (nqe_table_column(out, int32_t(i), &info) == NQE_OK) dt = DataType(info.dtype);
+            }
+            const ColumnExpr *c = group_expr[i]->as_column();
+            fields.emplace_back(std::nullopt, c ? below.field(c->resolve(below)).name() : "group_" + std::to_string(i), dt, false);
+        }
+        for (auto &op : aggr_ops) fields.push_back(op->data_field(below));
+        return NaiveSchema(fields);
+    }
+    // (input batches, predicate the operator applies itself): the plain operator has no predicate
+    virtual std::vector<RecordBatch> input_batches(PhysicalExprRef &pred_expr) {
+        pred_expr = nullptr;
+        return input->execute();
+    }
+    const NaiveSchema &schema() const override { return schema_; }
+    std::vector<PhysicalPlanRef> children() const override { return {input}; }
+    std::vector<RecordBatch> execute() override {
+        PhysicalExprRef pred_expr;
+        std::vector<RecordBatch> batches = input_batches(pred_expr);
+        if (batches.empty()) throw ErrorCode(ErrorCode::NotSupported, "aggregate over an empty batch list is not supported on the device path");
+        const ContextRef &ctx = batches[0].ctx();
+        const NaiveSchema &s = batches[0].schema();
+        std::vector<nqe_aggregate> aggs;
+        for (auto &op : aggr_ops) aggs.push_back(nqe_aggregate{int32_t(op->func()), int32_t(op->col_expr->resolve(s))});
+        std::vector<nqe_expr_node> pred, keys;
+        std::vector<int32_t> offs{0};
+        if (pred_expr) pred_expr->flatten(s, pred);
+        for (auto &e : group_expr) { e->flatten(s, keys); offs.push_back(int32_t(keys.size())); }
+        std::shared_ptr<nqe_table> single;
+        nqe_table *in = batches[0].raw();
+        if (batches.size() > 1) {
+            std::vector<const nqe_table *> parts;
+            for (auto &b : batches) parts.push_back(b.raw());
+            nqe_table *c = nullptr;
+            ctx->check(nqe_table_concat(ctx->raw(), parts.data(), int32_t(parts.size()), &c));
+            single.reset(c, [](nqe_table *p) { nqe_table_release(p); });
+            in = c;
+        }
+        nqe_table *out = nullptr;
+        ctx->check(nqe_group_aggregate_execute(ctx->raw(), in, pred.empty() ? nullptr : pred.data(), int32_t(pred.size()), keys.data(), offs.data(),
+                                               int32_t(group_expr.size()), aggs.data(), int32_t(aggs.size()), &out));
+        return {batches[0].with_table(output_schema(s, out), out)};
+    }
+};
+
 // ---------------------------------------------------------------- physical_plan/hash_join.rs:44-289
 struct HashJoin : PhysicalPlan {
     PhysicalPlanRef left, right; // LEFT = build side, RIGHT = probe side (quirk Q11)
@@ -883,6 +963,7 @@ inline void visit_physical_plan(const PhysicalPlan &plan, PhysicalPlanVisitor &v
 // the subtrees the device executes in one go; `rewrite(tree)->execute()` returns what `tree->execute()` returns.
 //   ProjectionPlan(SelectionPlan(x))         → FusedSelectionProjectionPlan(x)   nqe_selection_projection_execute
 //   PhysicalAggregatePlan(SelectionPlan(x))  → FusedSelectionAggregatePlan(x)    nqe_aggregate_execute with its predicate argument
+//   GroupedAggregatePlan(SelectionPlan(x))   → FusedSelectionGroupedAggregatePlan(x)  nqe_group_aggregate_execute with its predicate argument
 struct Materialized : PhysicalPlan { // an already-executed child (a fused operator falling back to the plain chain)
     std::vector<RecordBatch> batches;
     NaiveSchema schema_;
@@ -940,8 +1021,33 @@ struct FusedSelectionAggregatePlan : PhysicalAggregatePlan { // state and quirks
     }
 };
 
+struct FusedSelectionGroupedAggregatePlan : GroupedAggregatePlan { // the filter is nqe_group_aggregate_execute's predicate argument (Q20)
+    PhysicalExprRef predicate;
+    std::vector<RecordBatch> input_batches(PhysicalExprRef &pred_expr) override {
+        std::vector<RecordBatch> below = input->execute();
+        if (below.size() == 1) {
+            pred_expr = predicate;
+            return below;
+        }
+        pred_expr = nullptr; // several batches (Q3) or none (the selection's own error): the plain selection over what was produced
+        return SelectionPlan::create(Materialized::create(below, input->schema()), predicate)->execute();
+    }
+};
+
 // returns a NEW tree; nodes of the input tree are shared where they are kept (scans) and left as they were otherwise
 inline PhysicalPlanRef rewrite(const PhysicalPlanRef &plan) {
+    if (std::dynamic_pointer_cast<FusedSelectionGroupedAggregatePlan>(plan)) return plan;
+    if (auto g = std::dynamic_pointer_cast<GroupedAggregatePlan>(plan)) {
+        auto sel = std::dynamic_pointer_cast<SelectionPlan>(g->input);
+        if (!sel) return GroupedAggregatePlan::create_shared(g->group_expr, g->aggr_ops, rewrite(g->input));
+        auto f = std::make_shared<FusedSelectionGroupedAggregatePlan>();
+        f->predicate = sel->expr;
+        f->group_expr = g->group_expr;
+        f->aggr_ops = g->aggr_ops;
+        f->input = rewrite(sel->input);
+        f->schema_ = g->schema_;
+        return f;
+    }
     if (auto p = std::dynamic_pointer_cast<ProjectionPlan>(plan)) {
         auto sel = std::dynamic_pointer_cast<SelectionPlan>(p->input);
         if (sel && !p->schema_.fields().empty()) return FusedSelectionProjectionPlan::create(rewrite(sel->input), sel->expr, p->schema_, p->expr);

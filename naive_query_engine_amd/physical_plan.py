@@ -401,6 +401,57 @@ class PhysicalAggregatePlan(PhysicalPlan):
         return [DeviceRecordBatch(out_fields, out)]
 
 
+class GroupedAggregatePlan(PhysicalPlan):
+    """GROUP BY honouring EVERY group expression (quirk Q20; PhysicalAggregatePlan above keeps the reference's group_expr[0], Q8).  The
+    input batches are concatenated and ONE batch leaves: the key columns in key order, then one column per aggregate (Q13's logical
+    order), sorted ascending by the key tuple.  A row with a NULL in any key is dropped.  A key field takes the column's field name
+    for a bare ColumnExpr and `group_<i>` otherwise.  Nothing is kept between execute() calls."""
+
+    def __init__(self, group_expr, aggr_ops, input):
+        self.group_expr, self.aggr_ops, self.input = list(group_expr), list(aggr_ops), input
+        if not self.group_expr:
+            raise ErrorCode(Status.PlanError, "GroupedAggregatePlan: the list of group expressions is empty (the un-grouped form is PhysicalAggregatePlan's)")
+
+    @staticmethod
+    def create(group_expr: Sequence[PhysicalExpr], aggr_ops: Sequence[AggregateOperator], input: PhysicalPlan) -> "GroupedAggregatePlan":
+        return GroupedAggregatePlan(group_expr, aggr_ops, input)
+
+    def _key_fields(self, fields: Sequence[Field], dtypes=None) -> List[Field]:
+        out = []
+        for i, e in enumerate(self.group_expr):
+            cols = e.referenced_columns(fields)
+            name = fields[cols[0]].name if isinstance(e, ColumnExpr) else f"group_{i}"
+            # (before execution: integer arithmetic keeps its operands' type, so the first referenced column's type stands in)
+            dt = dtypes[i] if dtypes is not None else (fields[cols[0]].dtype if cols else DType.INT64)
+            out.append(Field(name, dt, False))
+        return out
+
+    def schema(self):
+        below = list(self.input.schema())
+        return self._key_fields(below) + [op.data_field(below) for op in self.aggr_ops]
+
+    def children(self):
+        return [self.input]
+
+    def _input_batches(self):
+        """(input batches, predicate expression the operator applies itself): the plain operator has no predicate"""
+        return self.input.execute(), None
+
+    def execute(self):
+        batches, pred_expr = self._input_batches()
+        if not batches:
+            raise ErrorCode(Status.NotSupported, "aggregate over an empty batch list is not supported on the device path")
+        ctx = _ctx_of(batches)
+        fields = batches[0].fields
+        table = batches[0].table if len(batches) == 1 else ctx.concat([b.table for b in batches])
+        aggs = [(op.func, op.col_expr.resolve(fields)) for op in self.aggr_ops]
+        pred = pred_expr.flatten(fields) if pred_expr is not None else None
+        out = ctx.group_aggregate(table, [e.flatten(fields) for e in self.group_expr], aggs, pred_nodes=pred)
+        k = len(self.group_expr)
+        out_fields = self._key_fields(fields, out.dtypes()[:k]) + [op.data_field(fields) for op in self.aggr_ops]
+        return [DeviceRecordBatch(out_fields, out)]
+
+
 def _merge_raw_state(ctx, parts, aggs):
     """Un-grouped raw states are single rows of (count,sum,min,max) per aggregate and the merge is
     associative, so the running state is simply the concatenation of the partial rows; it is folded

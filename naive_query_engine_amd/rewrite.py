@@ -4,6 +4,7 @@ aggregate over a selection, …) and substitutes the subtrees the device execute
 
     ProjectionPlan(SelectionPlan(x))          →  FusedSelectionProjectionPlan(x)      nqe_selection_projection_execute
     PhysicalAggregatePlan(SelectionPlan(x))   →  FusedSelectionAggregatePlan(x)       nqe_aggregate_execute with its predicate argument
+    GroupedAggregatePlan(SelectionPlan(x))    →  FusedSelectionGroupedAggregatePlan(x)  nqe_group_aggregate_execute with its predicate argument
     PhysicalLimitPlan(PhysicalSortPlan(x))    →  PhysicalSortPlan(x, fetch = n)       nqe_sort_execute with its fetch argument
 
 Everything else keeps its operator, with rewritten children.  The pass walks the tree through `children()` exactly as the
@@ -20,7 +21,7 @@ from __future__ import annotations
 from typing import Dict, List, Optional, Sequence
 
 from .arrow_host import ErrorCode, Field, RecordBatch, Status
-from .physical_plan import (CrossJoin, CsvConfig, CsvTable, DeviceRecordBatch, HashJoin, HashOuterJoin, MemTable, NaiveSchema, NestedLoopJoin, PhysicalAggregatePlan, PhysicalLimitPlan,
+from .physical_plan import (CrossJoin, CsvConfig, CsvTable, DeviceRecordBatch, GroupedAggregatePlan, HashJoin, HashOuterJoin, MemTable, NaiveSchema, NestedLoopJoin, PhysicalAggregatePlan, PhysicalLimitPlan,
                             PhysicalOffsetPlan, PhysicalPlan, PhysicalSortPlan, ProjectionPlan, ScanPlan, SelectionPlan, _ctx_of, _Materialized)
 
 
@@ -92,10 +93,32 @@ class FusedSelectionAggregatePlan(PhysicalAggregatePlan):
         return SelectionPlan.create(_Materialized(below, self.input.schema()), self.predicate).execute(), None
 
 
+class FusedSelectionGroupedAggregatePlan(GroupedAggregatePlan):
+    """GroupedAggregatePlan(SelectionPlan(input)): the filter is nqe_group_aggregate_execute's predicate argument (quirk Q20)."""
+
+    def __init__(self, group_expr, aggr_ops, predicate, input: PhysicalPlan):
+        super().__init__(group_expr, aggr_ops, input)
+        self.predicate = predicate
+
+    def unfused(self, child: PhysicalPlan) -> PhysicalPlan:
+        return GroupedAggregatePlan.create(self.group_expr, self.aggr_ops, SelectionPlan.create(child, self.predicate))
+
+    def _input_batches(self):
+        below = self.input.execute()
+        if len(below) == 1:
+            return below, self.predicate
+        # several batches (Q3), or none (the selection's own error): the plain selection over the batches already produced
+        return SelectionPlan.create(_Materialized(below, self.input.schema()), self.predicate).execute(), None
+
+
 def rewrite(plan: PhysicalPlan) -> PhysicalPlan:
     """the substitution pass (see the module docstring); returns a NEW tree, the input tree is left as it was"""
-    if isinstance(plan, (FusedSelectionProjectionPlan, FusedSelectionAggregatePlan, ScanPlan, _Materialized)):
+    if isinstance(plan, (FusedSelectionProjectionPlan, FusedSelectionAggregatePlan, FusedSelectionGroupedAggregatePlan, ScanPlan, _Materialized)):
         return plan
+    if isinstance(plan, GroupedAggregatePlan):
+        if isinstance(plan.input, SelectionPlan):
+            return FusedSelectionGroupedAggregatePlan(plan.group_expr, plan.aggr_ops, plan.input.expr, rewrite(plan.input.input))
+        return GroupedAggregatePlan.create(plan.group_expr, plan.aggr_ops, rewrite(plan.input))
     if isinstance(plan, ProjectionPlan):
         if isinstance(plan.input, SelectionPlan) and plan._schema:
             return FusedSelectionProjectionPlan(rewrite(plan.input.input), plan.input.expr, plan._schema, plan.expr)
