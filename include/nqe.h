@@ -609,6 +609,36 @@ nqe_status nqe_hash_join_probe_outer(nqe_ctx *ctx, const nqe_join_table *build, 
 nqe_status nqe_hash_join_unmatched_build(nqe_ctx *ctx, const nqe_join_table *build, const nqe_join_marks *marks,
                                          const int32_t *right_dtypes, int32_t num_right, nqe_table **out);
 
+/* ------------------------------------------------------------------ hash join on several keys
+ * HashJoin honouring every `on` pair — quirk Q21: the reference's DataFrame::join zips every key pair into `on`
+ * (logical_plan/dataframe.rs:109) and HashJoin::execute reads on[0] alone (hash_join.rs:134, :171).  The MATCH RELATION is the hash
+ * join's own, Q11 included, applied to every pair: two rows match iff for every pair i the raw 8-byte slot (the bytes between the
+ * slot's offsets for Utf8) of left[left_keys[i]] equals that of right[right_keys[i]]; key validity is ignored at every position.
+ * Per pair both Int64, both UInt64 or both Utf8 (pairs of different types may be mixed); the errors are the single-key join's for the
+ * first offending pair, in pair order.  The OUTPUT is exactly the single-key operators': all left columns, then all right columns,
+ * probe-row-major, matches in ascending build row, the NULL-extension / validity / null_count rules of the outer joins — no column
+ * that is not the caller's ever appears.  With one pair the calls forward to nqe_hash_join_build / _probe / _probe_outer / _execute:
+ * the result is theirs bit for bit.
+ *   nqe_hash_join_probe_keys: `flags` / `marks` as in nqe_hash_join_probe_outer; with flags = 0 and marks = NULL the inner probe's
+ *     tiers are taken.  nqe_join_marks_create, nqe_hash_join_unmatched_build and nqe_join_table_release accept a table from
+ *     nqe_hash_join_build_keys unchanged.
+ * Errors, decided before any launch or allocation: num_keys <= 0 NQE_ERR_PLAN (the empty `on`); num_keys > NQE_MAX_JOIN_KEYS
+ * NQE_ERR_NOT_SUPPORTED; a key index out of range NQE_ERR_LOGICAL; NULL index arrays or `out`, a num_keys that differs from the
+ * build's, unknown flag bits, foreign marks NQE_ERR_INVALID_ARGUMENT.  A table built on more than one key is refused with
+ * NQE_ERR_INVALID_ARGUMENT by nqe_hash_join_probe, nqe_hash_join_probe_outer and nqe_sharded_hash_join_probe.
+ * A build side of 2^30 rows or more whose keys need the tuple dictionary (a Utf8 pair, or integer spans whose product exceeds 2^62) is
+ * NQE_ERR_NOT_SUPPORTED; for integer keys that is known only after the range pass over the build keys has run.
+ * With more than one pair each side carries one hidden code column through the join, and both count against the join's 32-column
+ * limit: a composite join refuses left + right + 2 > 32 columns with NQE_ERR_NOT_SUPPORTED.
+ * Nothing is kept between calls except what the marks record.  NQE_JOIN_KEYS_FORCE_DICT=1 (a diagnostic switch, read per build call)
+ * sends integer tuples through the tuple dictionary instead of the packed codes; no result changes. */
+#define NQE_MAX_JOIN_KEYS 8
+nqe_status nqe_hash_join_build_keys(nqe_ctx *ctx, const nqe_table *left, const int32_t *left_keys, int32_t num_keys, nqe_join_table **out);
+nqe_status nqe_hash_join_probe_keys(nqe_ctx *ctx, const nqe_join_table *build, const nqe_table *right, const int32_t *right_keys,
+                                    int32_t num_keys, uint32_t flags, nqe_join_marks *marks /* may be NULL */, nqe_table **out);
+nqe_status nqe_hash_join_execute_keys(nqe_ctx *ctx, const nqe_table *left, const nqe_table *right, const int32_t *left_keys,
+                                      const int32_t *right_keys, int32_t num_keys, nqe_table **out); /* inner */
+
 /* ------------------------------------------------------------------ cross join
  * CrossJoin::execute (cross_join.rs:55-185) for one outer (left) batch and one inner (right)
  * batch; the caller loops over the batch pairs outer-major, one output batch per pair, and a side

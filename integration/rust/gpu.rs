@@ -117,6 +117,11 @@ extern "C" {
                                  out: *mut *mut NqeTable) -> i32;
     fn nqe_hash_join_unmatched_build(ctx: *mut NqeCtx, build: *const NqeJoinTable, marks: *const NqeJoinMarks, right_dtypes: *const i32, num_right: i32,
                                      out: *mut *mut NqeTable) -> i32;
+    fn nqe_hash_join_build_keys(ctx: *mut NqeCtx, left: *const NqeTable, left_keys: *const i32, num_keys: i32, out: *mut *mut NqeJoinTable) -> i32;
+    fn nqe_hash_join_probe_keys(ctx: *mut NqeCtx, build: *const NqeJoinTable, right: *const NqeTable, right_keys: *const i32, num_keys: i32, flags: u32,
+                                marks: *mut NqeJoinMarks, out: *mut *mut NqeTable) -> i32;
+    fn nqe_hash_join_execute_keys(ctx: *mut NqeCtx, left: *const NqeTable, right: *const NqeTable, left_keys: *const i32, right_keys: *const i32, num_keys: i32,
+                                  out: *mut *mut NqeTable) -> i32;
     fn nqe_cross_join_execute(ctx: *mut NqeCtx, left: *const NqeTable, right: *const NqeTable, out: *mut *mut NqeTable) -> i32;
     fn nqe_nested_loop_join_execute(ctx: *mut NqeCtx, left: *const NqeTable, right: *const NqeTable, left_key: i32, right_key: i32, out: *mut *mut NqeTable) -> i32;
     fn nqe_sort_execute(ctx: *mut NqeCtx, input: *const NqeTable, keys: *const NqeSortKey, num_keys: i32, fetch: i64, out: *mut *mut NqeTable) -> i32;
@@ -705,6 +710,70 @@ impl GpuExec for GpuHashOuterJoin {
     }
 }
 impl PhysicalPlan for GpuHashOuterJoin {
+    fn schema(&self) -> &NaiveSchema { &self.schema }
+    fn children(&self) -> Result<Vec<PhysicalPlanRef>> { Ok(vec![self.left.clone(), self.right.clone()]) }
+    fn execute(&self) -> Result<Vec<RecordBatch>> { self.ctx.download_all(&self.execute_device()?, &self.schema) }
+    fn as_any(&self) -> &dyn Any { self }
+    fn as_gpu(&self) -> Option<&dyn GpuExec> { Some(self) }
+}
+
+/// HashJoin honouring every `on` pair (quirk Q21; hash_join.rs:134, :171 read on[0] alone) and `join_type` as GpuHashOuterJoin does.
+/// The match relation is GpuHashJoin's, Q11 included, applied to every pair; batches, row order and NULL-extension are GpuHashOuterJoin's.
+/// Cross is a PlanError; an empty `on` is a PlanError after both children ran.
+#[derive(Debug)]
+pub struct GpuMultiKeyHashJoin {
+    left: PhysicalPlanRef, right: PhysicalPlanRef, on: Vec<(Column, Column)>, join_type: JoinType, schema: NaiveSchema, ctx: Arc<GpuCtx>,
+}
+impl GpuMultiKeyHashJoin {
+    pub fn create(ctx: Arc<GpuCtx>, left: PhysicalPlanRef, right: PhysicalPlanRef, on: Vec<(Column, Column)>, join_type: JoinType,
+                  schema: NaiveSchema) -> PhysicalPlanRef {
+        Arc::new(Self { left, right, on, join_type, schema, ctx })
+    }
+}
+impl GpuExec for GpuMultiKeyHashJoin {
+    fn execute_device(&self) -> Result<Vec<GpuBatch>> {
+        let (keep_probe, with_marks) = match self.join_type {
+            JoinType::Inner => (false, false), JoinType::Left => (false, true), JoinType::Right => (true, false),
+            JoinType::Cross => return Err(ErrorCode::PlanError("MultiKeyHashJoin: the join type must be Inner, Left or Right".to_string())),
+        };
+        let left = child_device(&self.ctx, &self.left)?;
+        let right = child_device(&self.ctx, &self.right)?;
+        if self.on.is_empty() { return Err(ErrorCode::PlanError("Inner Join on Conditions can't not be empty".to_string())); }
+        if left.is_empty() { return Err(ErrorCode::NotSupported("join with no left batches".to_string())); }
+        let single = self.ctx.concat(&left)?; // concat_batches (:132)
+        let mut lks: Vec<i32> = vec![];
+        let mut rks: Vec<i32> = vec![];
+        for (lc, rc) in self.on.iter() { // by NAME, first match (:134-136)
+            lks.push(self.left.schema().index_of(&lc.name)? as i32);
+            rks.push(self.right.schema().index_of(&rc.name)? as i32);
+        }
+        let mut jt = std::ptr::null_mut();
+        self.ctx.check(unsafe { nqe_hash_join_build_keys(self.ctx.0, single.table.0, lks.as_ptr(), lks.len() as i32, &mut jt) })?;
+        let jt = GpuJoinTable(jt);
+        let mut mk = std::ptr::null_mut();
+        if with_marks { self.ctx.check(unsafe { nqe_join_marks_create(self.ctx.0, jt.0, &mut mk) })?; }
+        let marks = GpuJoinMarks(mk); // (a null handle is released as a no-op)
+        let flags = if keep_probe { NQE_JOIN_KEEP_PROBE } else { 0 };
+        let mut out = vec![];
+        for b in right.iter() { // one output batch per probe batch
+            let mut t = std::ptr::null_mut();
+            self.ctx.check(unsafe { nqe_hash_join_probe_keys(self.ctx.0, jt.0, b.table.0, rks.as_ptr(), rks.len() as i32, flags, marks.0, &mut t) })?;
+            out.push(GpuBatch::wrap(t));
+        }
+        if with_marks { // the build rows no probe batch matched; dtypes from the probe child's schema
+            let dts: Vec<i32> = self.right.schema().fields().iter().map(|f| match f.data_type() {
+                DataType::Boolean => NQE_BOOLEAN, DataType::Int64 => NQE_INT64, DataType::UInt64 => NQE_UINT64,
+                DataType::Float64 => NQE_FLOAT64, DataType::Utf8 => NQE_UTF8, _ => -1, // → NQE_ERR_INVALID_ARGUMENT
+            }).collect();
+            let mut t = std::ptr::null_mut();
+            self.ctx.check(unsafe { nqe_hash_join_unmatched_build(self.ctx.0, jt.0, marks.0, dts.as_ptr(), dts.len() as i32, &mut t) })?;
+            out.push(GpuBatch::wrap(t));
+        }
+        drop(marks); // before the join table it is bound to
+        Ok(out)
+    }
+}
+impl PhysicalPlan for GpuMultiKeyHashJoin {
     fn schema(&self) -> &NaiveSchema { &self.schema }
     fn children(&self) -> Result<Vec<PhysicalPlanRef>> { Ok(vec![self.left.clone(), self.right.clone()]) }
     fn execute(&self) -> Result<Vec<RecordBatch>> { self.ctx.download_all(&self.execute_device()?, &self.schema) }

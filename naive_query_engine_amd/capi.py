@@ -29,7 +29,7 @@ SYMBOLS = [
     "nqe_filter", "nqe_selection_execute", "nqe_projection_execute", "nqe_selection_projection_execute",
     "nqe_aggregate_execute", "nqe_aggregate_partial", "nqe_aggregate_merge", "nqe_aggregate_merge_packed", "nqe_group_aggregate_execute", "nqe_hash_join_execute",
     "nqe_hash_join_build", "nqe_hash_join_probe", "nqe_join_table_release", "nqe_join_marks_create", "nqe_join_marks_release",
-    "nqe_hash_join_probe_outer", "nqe_hash_join_unmatched_build", "nqe_cross_join_execute", "nqe_nested_loop_join_execute", "nqe_sort_execute", "nqe_take", "nqe_synth_fill",
+    "nqe_hash_join_probe_outer", "nqe_hash_join_unmatched_build", "nqe_hash_join_build_keys", "nqe_hash_join_probe_keys", "nqe_hash_join_execute_keys", "nqe_cross_join_execute", "nqe_nested_loop_join_execute", "nqe_sort_execute", "nqe_take", "nqe_synth_fill",
     "nqe_device_alloc", "nqe_device_free",
     "nqe_comm_get_unique_id", "nqe_comm_rccl_version", "nqe_comm_create", "nqe_comm_create_custom", "nqe_comm_create_p2p", "nqe_comm_destroy", "nqe_comm_rank",
     "nqe_comm_world", "nqe_table_all_gather", "nqe_sharded_aggregate_execute", "nqe_sharded_hash_join_probe",
@@ -141,6 +141,9 @@ def lib():
         "nqe_join_marks_release": (i32, [vp]),
         "nqe_hash_join_probe_outer": (i32, [vp, vp, vp, i32, C.c_uint32, vp, pvp]),
         "nqe_hash_join_unmatched_build": (i32, [vp, vp, vp, C.POINTER(i32), i32, pvp]),
+        "nqe_hash_join_build_keys": (i32, [vp, vp, C.POINTER(i32), i32, pvp]),
+        "nqe_hash_join_probe_keys": (i32, [vp, vp, vp, C.POINTER(i32), i32, C.c_uint32, vp, pvp]),
+        "nqe_hash_join_execute_keys": (i32, [vp, vp, vp, C.POINTER(i32), C.POINTER(i32), i32, pvp]),
         "nqe_cross_join_execute": (i32, [vp, vp, vp, pvp]),
         "nqe_nested_loop_join_execute": (i32, [vp, vp, vp, i32, i32, pvp]),
         "nqe_sort_execute": (i32, [vp, vp, C.POINTER(NqeSortKey), i32, i64, pvp]),
@@ -428,6 +431,32 @@ class Context:
         h = C.c_void_p()
         self.check(lib().nqe_hash_join_unmatched_build(self.handle, jt.handle, marks.handle if marks is not None else None, da, len(right_dtypes), C.byref(h)))
         return Table(self, h)
+
+    @staticmethod
+    def _key_array(keys: Sequence[int]):
+        return (C.c_int32 * max(1, len(keys)))(*[int(k) for k in keys])
+
+    def hash_join_build_keys(self, left: "Table", left_keys: Sequence[int]) -> "JoinTable":
+        """nqe_hash_join_build_keys: the build side of a join on every key pair (quirk Q21); one key forwards to hash_join_build"""
+        h = C.c_void_p()
+        self.check(lib().nqe_hash_join_build_keys(self.handle, left.handle, self._key_array(left_keys), len(left_keys), C.byref(h)))
+        return JoinTable(self, h)
+
+    def hash_join_probe_keys(self, jt: "JoinTable", right: "Table", right_keys: Sequence[int], keep_probe: bool = False, marks: Optional["JoinMarks"] = None) -> "Table":
+        """one probe batch against a table from hash_join_build_keys; `keep_probe` / `marks` as in hash_join_probe_outer, without
+        either the inner probe"""
+        h = C.c_void_p()
+        self.check(lib().nqe_hash_join_probe_keys(self.handle, jt.handle, right.handle, self._key_array(right_keys), len(right_keys),
+                                                  JOIN_KEEP_PROBE if keep_probe else 0, marks.handle if marks is not None else None, C.byref(h)))
+        return Table(self, h, derived_from=(right,))
+
+    def hash_join_keys(self, left: "Table", right: "Table", left_keys: Sequence[int], right_keys: Sequence[int]) -> "Table":
+        """nqe_hash_join_execute_keys: the inner join on left[left_keys[i]] == right[right_keys[i]] for every i"""
+        if len(left_keys) != len(right_keys):
+            raise ValueError("hash_join_keys: as many left keys as right keys")
+        h = C.c_void_p()
+        self.check(lib().nqe_hash_join_execute_keys(self.handle, left.handle, right.handle, self._key_array(left_keys), self._key_array(right_keys), len(left_keys), C.byref(h)))
+        return Table(self, h, derived_from=(right,))
 
     def cross_join(self, left: "Table", right: "Table") -> "Table":
         """CrossJoin::execute for one batch pair (quirk Q15): left[j % L] beside right[j % R] for j < L*R, no validity"""

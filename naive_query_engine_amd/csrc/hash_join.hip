@@ -699,8 +699,11 @@ std::unique_ptr<nqe_table> probe_dense_payload(nqe_ctx *ctx, const nqe_join_tabl
     // every row, the output row of a probe row is the probe row, and ONE pass (no presence pass, no scan, the probe keys read
     // once) writes everything — while checking every key against the range.  A key outside it discards the output, and this
     // join table (and, through the context's join hints, this join) takes the two-pass form from then on.
-    const uint64_t jhint = join_hint_key(jt, rk, n);
-    if (ctx->join_hints.count(jhint)) jt->all_match_failed = true;
+    // (a table built on several keys takes no hint and leaves none: both of its key buffers are pool-allocated code columns, whose
+    // addresses recur across unrelated joins of equal sizes — the verdict stays with the table, all_match_failed)
+    const bool hinted = !jt->keys;
+    const uint64_t jhint = hinted ? join_hint_key(jt, rk, n) : 0;
+    if (hinted && ctx->join_hints.count(jhint)) jt->all_match_failed = true;
     if (jt->dense_full && !jt->all_match_failed && n > 0) {
         FusedCols fc;
         auto out = fused_output(ctx, jt, right, right_key, rk, n, left, may_share, fc);
@@ -712,8 +715,10 @@ std::unique_ptr<nqe_table> probe_dense_payload(nqe_ctx *ctx, const nqe_join_tabl
                (const uint64_t *)nullptr, (const uint64_t *)nullptr, jt->dense_min, (const uint32_t *)nullptr, fc, jt->dense_span, (int *)miss->ptr);
         if (!read_scalar(ctx, (const int *)miss->ptr)) return out;
         jt->all_match_failed = true;
-        if (ctx->join_hints.size() >= 256) ctx->join_hints.clear();
-        ctx->join_hints[jhint] = 1;
+        if (hinted) {
+            if (ctx->join_hints.size() >= 256) ctx->join_hints.clear();
+            ctx->join_hints[jhint] = 1;
+        }
     }
     // two passes: presence test + counts, scan, then one fused write of every output column
     BufRef counts;
@@ -1176,7 +1181,8 @@ std::unique_ptr<nqe_table> unmatched_build(nqe_ctx *ctx, const nqe_join_table *j
     auto out = std::make_unique<nqe_table>();
     out->ctx = ctx;
     out->rows = km.total;
-    for (auto &c : jt->left_cols) out->cols.push_back(compact_column(ctx, c, km));
+    const size_t visible = jt->left_cols.size() - (jt->keys ? 1 : 0); // (the hidden code column of a join on several keys, the last one, is not gathered)
+    for (size_t c = 0; c < visible; ++c) out->cols.push_back(compact_column(ctx, jt->left_cols[c], km));
     for (int k = 0; k < num_right; ++k) out->cols.push_back(null_column(ctx, right_dtypes[k], km.total));
     count_nulls_exact(ctx, out.get());
     sync(ctx);
@@ -1198,7 +1204,35 @@ std::unique_ptr<nqe_table> probe_table(nqe_ctx *ctx, const nqe_join_table *jt, c
     return probe_duplicates(ctx, jt, right, right_key, rk, rk_orig);
 }
 
+// a table built on several keys is probed through nqe_hash_join_probe_keys alone: its key is a code column the caller never sees
+void refuse_tuple_table(const nqe_join_table *jt, const char *who) {
+    if (jt->keys) fail(NQE_ERR_INVALID_ARGUMENT, std::string(who) + ": the join table was built on several keys (nqe_hash_join_probe_keys probes it)");
+}
+void check_outer_args(nqe_ctx *ctx, const nqe_join_table *build, uint32_t flags, const nqe_join_marks *marks) {
+    if (flags & ~NQE_JOIN_KEEP_PROBE) fail(NQE_ERR_INVALID_ARGUMENT, "nqe_hash_join_probe_outer: unknown flag bits");
+    if (marks && (marks->ctx != ctx || marks->table != build || marks->rows != build->left_rows))
+        fail(NQE_ERR_INVALID_ARGUMENT, "nqe_hash_join_probe_outer: the marks belong to another join table or context");
+}
+
 } // namespace
+
+// ---- the doors of join_keys.hip (join_keys_state.hpp)
+void join_check_key_types(int ldt, int rdt) { check_key_types(ldt, rdt); }
+nqe_join_table *join_build_coded(nqe_ctx *ctx, const nqe_table *left_with_code, std::shared_ptr<const JoinKeysState> keys) {
+    flags_reset(ctx);
+    std::unique_ptr<nqe_join_table> jt = build_table(ctx, left_with_code, int(left_with_code->cols.size()) - 1);
+    jt->keys = std::move(keys);
+    return jt.release();
+}
+const JoinKeysState *join_table_keys(const nqe_join_table *jt) { return jt->keys.get(); }
+size_t join_table_columns(const nqe_join_table *jt) { return jt->left_cols.size(); }
+void join_check_outer_args(nqe_ctx *ctx, const nqe_join_table *jt, uint32_t flags, const nqe_join_marks *marks) { check_outer_args(ctx, jt, flags, marks); }
+nqe_table *join_probe_coded(nqe_ctx *ctx, const nqe_join_table *jt, const nqe_table *right_with_code, uint32_t flags, nqe_join_marks *marks) {
+    const int key = int(right_with_code->cols.size()) - 1;
+    flags_reset(ctx);
+    if (flags == 0 && !marks) return probe_table(ctx, jt, right_with_code, key).release();
+    return probe_outer(ctx, jt, right_with_code, key, (flags & NQE_JOIN_KEEP_PROBE) != 0, marks ? (uint32_t *)marks->bits->ptr : (uint32_t *)nullptr).release();
+}
 
 } // namespace nqe
 
@@ -1218,6 +1252,7 @@ nqe_status nqe_hash_join_probe(nqe_ctx *ctx, const nqe_join_table *build, const 
                                nqe_table **out) {
     NQE_API_BEGIN(ctx)
     if (!ctx || !build || !right || !out) fail(NQE_ERR_INVALID_ARGUMENT, "bad arguments");
+    refuse_tuple_table(build, "nqe_hash_join_probe");
     flags_reset(ctx);
     *out = probe_table(ctx, build, right, right_key).release();
     NQE_API_END()
@@ -1249,9 +1284,8 @@ nqe_status nqe_hash_join_probe_outer(nqe_ctx *ctx, const nqe_join_table *build, 
                                      nqe_join_marks *marks, nqe_table **out) {
     NQE_API_BEGIN(ctx)
     if (!ctx || !build || !right || !out) fail(NQE_ERR_INVALID_ARGUMENT, "bad arguments");
-    if (flags & ~NQE_JOIN_KEEP_PROBE) fail(NQE_ERR_INVALID_ARGUMENT, "nqe_hash_join_probe_outer: unknown flag bits");
-    if (marks && (marks->ctx != ctx || marks->table != build || marks->rows != build->left_rows))
-        fail(NQE_ERR_INVALID_ARGUMENT, "nqe_hash_join_probe_outer: the marks belong to another join table or context");
+    refuse_tuple_table(build, "nqe_hash_join_probe_outer");
+    check_outer_args(ctx, build, flags, marks);
     flags_reset(ctx);
     *out = probe_outer(ctx, build, right, right_key, (flags & NQE_JOIN_KEEP_PROBE) != 0, marks ? (uint32_t *)marks->bits->ptr : (uint32_t *)nullptr).release();
     NQE_API_END()

@@ -2,6 +2,7 @@
 // Included once, by hash_join.hip (through the two kernel headers); which build form fills which field is mapped in hash_join.hip.
 #pragma once
 #include "device_utils.hpp"
+#include "join_keys_state.hpp"
 #include "nqe_internal.hpp"
 
 namespace nqe {
@@ -12,7 +13,7 @@ constexpr uint64_t GOLD = 0x9E3779B97F4A7C15ull;
 constexpr int JT_ROWS = 4096; // probe tile
 constexpr int JT_BLOCK = 256;
 constexpr int JT_ITERS = JT_ROWS / JT_BLOCK;
-constexpr int MAX_JOIN_COLS = 32;
+constexpr int MAX_JOIN_COLS = JOIN_MAX_COLS;
 constexpr int UNIQUE_MAX_PROBE = 128; // longest probe sequence of the sort-free inserts (beyond it: the sort-based build)
 constexpr int PW_TILE = 1024; // probe rows per tile (= JT_ROWS / 4); tile_offsets are per JT_ROWS, so 4 sub-tiles share one base
 // 16 rows per lane in flight: the kernel is bound by the latency of its gathers, and memory-level parallelism per wave
@@ -152,4 +153,7 @@ struct nqe_join_table {
     nqe::PackedPairs pp{}; // pbits == 0: the 16-byte form
     // Utf8 join keys: the build strings are encoded to representative-row codes (strings.hip)
     nqe::Utf8Dict dict;
+    // a join on several keys (quirk Q21, join_keys.hip): the last of left_cols is the hidden code column this table is keyed by, and
+    // this is what turns a probe tuple into a code; null for a table built on one key
+    std::shared_ptr<const nqe::JoinKeysState> keys;
 };

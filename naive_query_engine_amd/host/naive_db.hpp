@@ -790,6 +790,74 @@ struct HashOuterJoin : PhysicalPlan {
     }
 };
 
+// ---------------------------------------------------------------- hash join on several keys (no reference file: hash_join.rs:134, :171 read on[0] alone)
+// Quirk Q21: HashJoin honouring every `on` pair, and join_type as HashOuterJoin does.  The match relation is HashJoin's, Q11 included,
+// applied to every pair (LEFT child = build side, RIGHT = probe side, key validity ignored at every position).  Every pair is resolved by
+// NAME, first match (Q12): the left names against the first left batch, the right names per probe batch.  Batches, row order and
+// NULL-extension are HashOuterJoin's; with one pair its batches equal HashOuterJoin's.  Cross is a PlanError; an empty `on` is a PlanError
+// after both children ran.  Nothing is kept between execute() calls (no Q11 re-execution duplication).
+struct MultiKeyHashJoin : PhysicalPlan {
+    PhysicalPlanRef left, right;
+    std::vector<std::pair<Column, Column>> on;
+    JoinType join_type = JoinType::Inner;
+    NaiveSchema schema_;
+    static PhysicalPlanRef create(PhysicalPlanRef left, PhysicalPlanRef right, std::vector<std::pair<Column, Column>> on, JoinType jt, NaiveSchema schema) {
+        auto p = std::make_shared<MultiKeyHashJoin>();
+        p->left = std::move(left); p->right = std::move(right); p->on = std::move(on); p->join_type = jt; p->schema_ = std::move(schema);
+        return p;
+    }
+    const NaiveSchema &schema() const override { return schema_; }
+    std::vector<PhysicalPlanRef> children() const override { return {left, right}; }
+    std::vector<RecordBatch> execute() override {
+        if (join_type == JoinType::Cross) throw ErrorCode(ErrorCode::PlanError, "MultiKeyHashJoin: the join type must be Inner, Left or Right");
+        std::vector<RecordBatch> lb = left->execute(), rb = right->execute();
+        if (on.empty()) throw ErrorCode(ErrorCode::PlanError, "Inner Join on Conditions can't not be empty");
+        if (lb.empty()) throw ErrorCode(ErrorCode::NotSupported, "join with an empty left batch list is not supported on the device path");
+        const ContextRef &ctx = lb[0].ctx();
+        std::shared_ptr<nqe_table> single;
+        nqe_table *ltab = lb[0].raw();
+        if (lb.size() > 1) { // concat_batches (:132)
+            std::vector<const nqe_table *> parts;
+            for (auto &b : lb) parts.push_back(b.raw());
+            nqe_table *c = nullptr;
+            ctx->check(nqe_table_concat(ctx->raw(), parts.data(), int32_t(parts.size()), &c));
+            single.reset(c, [](nqe_table *p) { nqe_table_release(p); });
+            ltab = c;
+        }
+        std::vector<int32_t> lkeys, rkeys;
+        for (auto &p : on) lkeys.push_back(int32_t(ColumnExpr::try_create(p.first.name, std::nullopt)->resolve(lb[0].schema()))); // by NAME (:134-136)
+        nqe_join_table *jt = nullptr;
+        ctx->check(nqe_hash_join_build_keys(ctx->raw(), ltab, lkeys.data(), int32_t(lkeys.size()), &jt));
+        std::shared_ptr<nqe_join_table> jguard(jt, [](nqe_join_table *p) { nqe_join_table_release(p); });
+        nqe_join_marks *marks = nullptr;
+        if (join_type == JoinType::Left) ctx->check(nqe_join_marks_create(ctx->raw(), jt, &marks));
+        std::shared_ptr<nqe_join_marks> mguard(marks, [](nqe_join_marks *p) { nqe_join_marks_release(p); });
+        auto joined = [&](const NaiveSchema &rs, nqe_table *t) {
+            if (int32_t(schema_.fields().size()) == nqe_table_num_columns(t)) return schema_;
+            std::vector<NaiveField> f = lb[0].schema().fields();
+            for (auto &x : rs.fields()) f.push_back(x);
+            return NaiveSchema(f);
+        };
+        std::vector<RecordBatch> out;
+        for (auto &b : rb) { // one output batch per probe batch
+            rkeys.clear();
+            for (auto &p : on) rkeys.push_back(int32_t(ColumnExpr::try_create(p.second.name, std::nullopt)->resolve(b.schema())));
+            nqe_table *t = nullptr;
+            ctx->check(nqe_hash_join_probe_keys(ctx->raw(), jt, b.raw(), rkeys.data(), int32_t(rkeys.size()), join_type == JoinType::Right ? NQE_JOIN_KEEP_PROBE : 0u, marks, &t));
+            out.push_back(b.with_table(joined(b.schema(), t), t));
+        }
+        if (join_type == JoinType::Left) { // the build rows no probe batch matched; dtypes from the probe child's schema
+            const NaiveSchema &rs = rb.empty() ? right->schema() : rb[0].schema();
+            std::vector<int32_t> dts;
+            for (auto &f : rs.fields()) dts.push_back(int32_t(f.data_type));
+            nqe_table *t = nullptr;
+            ctx->check(nqe_hash_join_unmatched_build(ctx->raw(), jt, marks, dts.data(), int32_t(dts.size()), &t));
+            out.push_back(lb[0].with_table(joined(rs, t), t));
+        }
+        return out;
+    }
+};
+
 // ---------------------------------------------------------------- physical_plan/cross_join.rs:26-192
 // One output batch per (outer, inner) batch pair, outer-major.  Quirk Q15: output row j takes left row j % L and right row j % R
 // (a Cartesian product only when gcd(L, R) = 1); no output column has a validity bitmap; nothing is kept between execute() calls.
@@ -1080,6 +1148,7 @@ inline PhysicalPlanRef rewrite(const PhysicalPlanRef &plan) {
     if (auto srt = std::dynamic_pointer_cast<PhysicalSortPlan>(plan)) return PhysicalSortPlan::create(rewrite(srt->input), srt->sort_exprs, srt->fetch);
     if (auto o = std::dynamic_pointer_cast<PhysicalOffsetPlan>(plan)) return PhysicalOffsetPlan::create(rewrite(o->input), o->n);
     if (auto o = std::dynamic_pointer_cast<HashOuterJoin>(plan)) return HashOuterJoin::create(rewrite(o->left), rewrite(o->right), o->on, o->join_type, o->schema_);
+    if (auto m = std::dynamic_pointer_cast<MultiKeyHashJoin>(plan)) return MultiKeyHashJoin::create(rewrite(m->left), rewrite(m->right), m->on, m->join_type, m->schema_);
     if (auto j = std::dynamic_pointer_cast<HashJoin>(plan)) return HashJoin::create(rewrite(j->left), rewrite(j->right), j->on, j->join_type, j->schema_);
     if (auto c = std::dynamic_pointer_cast<CrossJoin>(plan)) return CrossJoin::create(rewrite(c->left), rewrite(c->right), c->join_type, c->schema_);
     if (auto n = std::dynamic_pointer_cast<NestedLoopJoin>(plan)) return NestedLoopJoin::create(rewrite(n->left), rewrite(n->right), n->on, n->join_type, n->schema_);

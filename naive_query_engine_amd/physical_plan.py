@@ -569,6 +569,57 @@ class HashOuterJoin(PhysicalPlan):
         return out
 
 
+# ----------------------------------------------------------------------------- hash join on several keys
+class MultiKeyHashJoin(PhysicalPlan):
+    """HashJoin honouring every `on` pair (quirk Q21; the reference's HashJoin reads on[0] alone) and `join_type` as HashOuterJoin
+    does.  The match relation is HashJoin's, Q11 included, applied to every pair: LEFT child = build side, RIGHT = probe side, key
+    validity ignored at every position.  Every pair is resolved by NAME, first match (Q12): the left names against the first left
+    batch, the right names per probe batch.  Batches, row order and NULL-extension are HashOuterJoin's; with one pair its batches
+    equal HashOuterJoin's.  Cross raises PlanError; an empty `on` raises PlanError after both children ran.  Nothing is kept between
+    execute() calls (no Q11 re-execution duplication)."""
+
+    def __init__(self, left, right, on, join_type, schema):
+        self.left, self.right, self.on, self.join_type, self._schema = left, right, list(on), join_type, list(schema)
+
+    @staticmethod
+    def create(left: PhysicalPlan, right: PhysicalPlan, on: Sequence[Tuple[ColumnRef, ColumnRef]], join_type, schema: NaiveSchema) -> "MultiKeyHashJoin":
+        return MultiKeyHashJoin(left, right, on, join_type, schema)
+
+    def schema(self):
+        return self._schema
+
+    def children(self):
+        return [self.left, self.right]
+
+    def execute(self):
+        if self.join_type not in (JoinType.Inner, JoinType.Left, JoinType.Right):
+            raise ErrorCode(Status.PlanError, "MultiKeyHashJoin: the join type must be Inner, Left or Right")
+        lb = self.left.execute()
+        rb = self.right.execute()
+        if not self.on:  # as HashJoin (hash_join.rs:125-129)
+            raise ErrorCode(Status.PlanError, "Inner Join on Conditions can't not be empty")
+        ctx = _ctx_of(lb or rb)
+        if not lb:
+            raise ErrorCode(Status.NotSupported, "join with an empty left batch list is not supported on the device path")
+        ltab = lb[0].table if len(lb) == 1 else ctx.concat([b.table for b in lb])  # concat_batches (:132)
+        lkeys = [ColumnExpr.try_create(l.name, None).resolve(lb[0].fields) for l, _ in self.on]  # by NAME, first match (:134-136)
+        jt = ctx.hash_join_build_keys(ltab, lkeys)
+        marks = ctx.join_marks(jt) if self.join_type == JoinType.Left else None
+        ncols = len(lb[0].fields) + len(self.right.schema())
+        out = []
+        for b in rb:  # one output batch per probe batch
+            rkeys = [ColumnExpr.try_create(r.name, None).resolve(b.fields) for _, r in self.on]
+            t = ctx.hash_join_probe_keys(jt, b.table, rkeys, keep_probe=self.join_type == JoinType.Right, marks=marks)
+            fields = self._schema if len(self._schema) == t.num_columns else list(lb[0].fields) + list(b.fields)
+            out.append(DeviceRecordBatch(fields, t))
+        if self.join_type == JoinType.Left:  # the build rows no probe batch matched; dtypes from the probe child's schema
+            rfields = list(rb[0].fields) if rb else list(self.right.schema())
+            t = ctx.hash_join_unmatched_build(jt, marks, [f.dtype for f in rfields])
+            fields = self._schema if len(self._schema) == ncols else list(lb[0].fields) + rfields
+            out.append(DeviceRecordBatch(fields, t))
+        return out
+
+
 # ----------------------------------------------------------------------------- cross join
 class CrossJoin(PhysicalPlan):
     """src/physical_plan/cross_join.rs:26-192 — one output batch per (outer, inner) batch pair, outer-major; quirk Q15: with L and R

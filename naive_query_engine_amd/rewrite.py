@@ -21,7 +21,7 @@ from __future__ import annotations
 from typing import Dict, List, Optional, Sequence
 
 from .arrow_host import ErrorCode, Field, RecordBatch, Status
-from .physical_plan import (CrossJoin, CsvConfig, CsvTable, DeviceRecordBatch, GroupedAggregatePlan, HashJoin, HashOuterJoin, MemTable, NaiveSchema, NestedLoopJoin, PhysicalAggregatePlan, PhysicalLimitPlan,
+from .physical_plan import (CrossJoin, CsvConfig, CsvTable, DeviceRecordBatch, GroupedAggregatePlan, HashJoin, HashOuterJoin, MemTable, MultiKeyHashJoin, NaiveSchema, NestedLoopJoin, PhysicalAggregatePlan, PhysicalLimitPlan,
                             PhysicalOffsetPlan, PhysicalPlan, PhysicalSortPlan, ProjectionPlan, ScanPlan, SelectionPlan, _ctx_of, _Materialized)
 
 
@@ -140,6 +140,8 @@ def rewrite(plan: PhysicalPlan) -> PhysicalPlan:
         return PhysicalOffsetPlan.create(rewrite(plan.input), plan.n)
     if isinstance(plan, HashOuterJoin):
         return HashOuterJoin.create(rewrite(plan.left), rewrite(plan.right), plan.on, plan.join_type, plan._schema)
+    if isinstance(plan, MultiKeyHashJoin):
+        return MultiKeyHashJoin.create(rewrite(plan.left), rewrite(plan.right), plan.on, plan.join_type, plan._schema)
     if isinstance(plan, HashJoin):
         return HashJoin.create(rewrite(plan.left), rewrite(plan.right), plan.on, plan.join_type, plan._schema)
     if isinstance(plan, CrossJoin):
