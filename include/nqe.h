@@ -639,6 +639,42 @@ nqe_status nqe_hash_join_probe_keys(nqe_ctx *ctx, const nqe_join_table *build, c
 nqe_status nqe_hash_join_execute_keys(nqe_ctx *ctx, const nqe_table *left, const nqe_table *right, const int32_t *left_keys,
                                       const int32_t *right_keys, int32_t num_keys, nqe_table **out); /* inner */
 
+/* ------------------------------------------------------------------ semi and anti hash joins
+ * "Which rows of this table have a partner in that one", and the complement: the join behind WHERE k IN (SELECT ...), EXISTS and
+ * NOT EXISTS — quirk Q22.  The reference has no such operator (JoinType is {Inner, Left, Right, Cross}, logical_plan/plan.rs:134-139);
+ * it is defined against this library's own inner join.  Left = build side, right = probe side; the MATCH RELATION is
+ * nqe_hash_join_probe_keys', Q11 included: raw 8-byte slots for Int64 / UInt64 keys, the bytes between the offsets for Utf8 keys, key
+ * validity ignored at every position, the same key dtype rules and errors.
+ *   probe SEMI  (nqe_hash_join_probe_semi, flags without NQE_SEMI_ANTI): one batch per probe batch with EVERY RIGHT COLUMN AND NOTHING
+ *               ELSE, holding the probe rows that have at least one match, each once, in probe order.  Its rows are the distinct probe
+ *               rows of the inner join's output over the same tables (duplicate build keys do not repeat a probe row).
+ *   probe ANTI  (NQE_SEMI_ANTI): the same with the probe rows that have no match; SEMI and ANTI partition the batch.
+ *   build SEMI / ANTI: pass marks to any number of nqe_hash_join_probe_semi calls (`out` = NULL is the mark-only pass: no keep mask,
+ *               no counts, no compaction), then nqe_hash_join_marked_build gives one batch with the build rows that matched in some
+ *               batch (flags = 0) or in none (NQE_SEMI_ANTI), in ascending build row, with the visible left columns only — no right
+ *               column and never the hidden code column of a table built on several keys.  ANTI's columns are the first n_left
+ *               columns of nqe_hash_join_unmatched_build, bit for bit.
+ * The probe door serves tables from nqe_hash_join_build and from nqe_hash_join_build_keys; num_keys must equal the build's.
+ * Output columns are what the selection's compaction gives for the keep mask: values of valid rows bit for bit, validity preserved
+ * (a validity buffer is present exactly when the source column has one), null_count exact, Boolean and Utf8 payload columns allowed.
+ * An empty side or no kept row gives a 0-row table with every column.  Nothing is kept between calls except what the marks record.
+ * NQE_SEMI_NULL_KEY_UNMATCHED is the EXISTS / NOT EXISTS / IN reading: a probe row with a NULL at ANY key position matches nothing —
+ * SEMI drops it, ANTI keeps it, and it sets no mark.  With this flag a build key column that has a validity buffer and a null_count
+ * other than 0 is NQE_ERR_NOT_SUPPORTED (excluding NULL build rows would need the table rebuilt without them).  NOT IN's three-valued
+ * rule — one NULL on the build side empties the result — is NOT implemented: the caller tests the build side for NULLs itself.
+ * Errors, decided before any launch or allocation, in this order: NULL ctx / build / right / right_keys, or `out` and `marks` both NULL:
+ * NQE_ERR_INVALID_ARGUMENT; num_keys <= 0 NQE_ERR_PLAN; num_keys > NQE_MAX_JOIN_KEYS NQE_ERR_NOT_SUPPORTED; a num_keys that differs
+ * from the build's, unknown flag bits, foreign marks NQE_ERR_INVALID_ARGUMENT; a key index out of range NQE_ERR_LOGICAL; the key dtype
+ * errors of the join; the NULL-flag refusal above.  nqe_hash_join_marked_build: NULL or foreign marks, or flag bits other than
+ * NQE_SEMI_ANTI, NQE_ERR_INVALID_ARGUMENT.  The join's 32-column limit does not apply: columns are compacted one at a time and no
+ * build column is written. */
+#define NQE_SEMI_ANTI 1u
+#define NQE_SEMI_NULL_KEY_UNMATCHED 2u
+nqe_status nqe_hash_join_probe_semi(nqe_ctx *ctx, const nqe_join_table *build, const nqe_table *right, const int32_t *right_keys,
+                                    int32_t num_keys, uint32_t flags, nqe_join_marks *marks /* may be NULL */, nqe_table **out /* NULL: mark only */);
+nqe_status nqe_hash_join_marked_build(nqe_ctx *ctx, const nqe_join_table *build, const nqe_join_marks *marks, uint32_t flags /* NQE_SEMI_ANTI or 0 */,
+                                      nqe_table **out);
+
 /* ------------------------------------------------------------------ cross join
  * CrossJoin::execute (cross_join.rs:55-185) for one outer (left) batch and one inner (right)
  * batch; the caller loops over the batch pairs outer-major, one output batch per pair, and a side

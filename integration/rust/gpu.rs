@@ -77,6 +77,8 @@ pub enum NqeTable {}
 pub enum NqeJoinTable {}
 pub enum NqeJoinMarks {}
 pub const NQE_JOIN_KEEP_PROBE: u32 = 1;
+pub const NQE_SEMI_ANTI: u32 = 1;
+pub const NQE_SEMI_NULL_KEY_UNMATCHED: u32 = 2;
 pub enum NqeComm {}
 
 // nqe_expr_kind; nqe_unary_operator is `enum UnaryOperator` in declaration order (expression.rs:392-422): Abs = 0, Sin = 1, Cos = 2, Tan = 3,
@@ -122,6 +124,9 @@ extern "C" {
                                 marks: *mut NqeJoinMarks, out: *mut *mut NqeTable) -> i32;
     fn nqe_hash_join_execute_keys(ctx: *mut NqeCtx, left: *const NqeTable, right: *const NqeTable, left_keys: *const i32, right_keys: *const i32, num_keys: i32,
                                   out: *mut *mut NqeTable) -> i32;
+    fn nqe_hash_join_probe_semi(ctx: *mut NqeCtx, build: *const NqeJoinTable, right: *const NqeTable, right_keys: *const i32, num_keys: i32, flags: u32,
+                                marks: *mut NqeJoinMarks, out: *mut *mut NqeTable) -> i32;
+    fn nqe_hash_join_marked_build(ctx: *mut NqeCtx, build: *const NqeJoinTable, marks: *const NqeJoinMarks, flags: u32, out: *mut *mut NqeTable) -> i32;
     fn nqe_cross_join_execute(ctx: *mut NqeCtx, left: *const NqeTable, right: *const NqeTable, out: *mut *mut NqeTable) -> i32;
     fn nqe_nested_loop_join_execute(ctx: *mut NqeCtx, left: *const NqeTable, right: *const NqeTable, left_key: i32, right_key: i32, out: *mut *mut NqeTable) -> i32;
     fn nqe_sort_execute(ctx: *mut NqeCtx, input: *const NqeTable, keys: *const NqeSortKey, num_keys: i32, fetch: i64, out: *mut *mut NqeTable) -> i32;
@@ -774,6 +779,75 @@ impl GpuExec for GpuMultiKeyHashJoin {
     }
 }
 impl PhysicalPlan for GpuMultiKeyHashJoin {
+    fn schema(&self) -> &NaiveSchema { &self.schema }
+    fn children(&self) -> Result<Vec<PhysicalPlanRef>> { Ok(vec![self.left.clone(), self.right.clone()]) }
+    fn execute(&self) -> Result<Vec<RecordBatch>> { self.ctx.download_all(&self.execute_device()?, &self.schema) }
+    fn as_any(&self) -> &dyn Any { self }
+    fn as_gpu(&self) -> Option<&dyn GpuExec> { Some(self) }
+}
+
+/// Which side of a semi / anti join is kept, and with which polarity (quirk Q22; the reference's JoinType is {Inner, Left, Right, Cross})
+#[derive(Debug, Clone, Copy, PartialEq)]
+pub enum SemiJoinType { ProbeSemi, ProbeAnti, BuildSemi, BuildAnti }
+
+/// Which rows of one child have a partner in the other (quirk Q22): WHERE k IN (SELECT ...), EXISTS, NOT EXISTS.  The match relation is
+/// GpuMultiKeyHashJoin's, Q11 included — unless `null_key_unmatched`: then a probe row with a NULL at any key position matches nothing.
+/// ProbeSemi / ProbeAnti: one output batch per probe batch with the right columns alone; BuildSemi / BuildAnti: one final batch, always
+/// emitted, of the left columns alone, in ascending build row.  `schema` is the kept side's schema.
+#[derive(Debug)]
+pub struct GpuHashSemiJoin {
+    left: PhysicalPlanRef, right: PhysicalPlanRef, on: Vec<(Column, Column)>, semi_type: SemiJoinType, schema: NaiveSchema, null_key_unmatched: bool,
+    ctx: Arc<GpuCtx>,
+}
+impl GpuHashSemiJoin {
+    pub fn create(ctx: Arc<GpuCtx>, left: PhysicalPlanRef, right: PhysicalPlanRef, on: Vec<(Column, Column)>, semi_type: SemiJoinType, schema: NaiveSchema,
+                  null_key_unmatched: bool) -> PhysicalPlanRef {
+        Arc::new(Self { left, right, on, semi_type, schema, null_key_unmatched, ctx })
+    }
+}
+impl GpuExec for GpuHashSemiJoin {
+    fn execute_device(&self) -> Result<Vec<GpuBatch>> {
+        let build_side = self.semi_type == SemiJoinType::BuildSemi || self.semi_type == SemiJoinType::BuildAnti;
+        let anti = self.semi_type == SemiJoinType::ProbeAnti || self.semi_type == SemiJoinType::BuildAnti;
+        let left = child_device(&self.ctx, &self.left)?;
+        let right = child_device(&self.ctx, &self.right)?;
+        if self.on.is_empty() { return Err(ErrorCode::PlanError("Inner Join on Conditions can't not be empty".to_string())); }
+        if left.is_empty() { return Err(ErrorCode::NotSupported("join with no left batches".to_string())); }
+        let single = self.ctx.concat(&left)?; // concat_batches (:132)
+        let mut lks: Vec<i32> = vec![];
+        let mut rks: Vec<i32> = vec![];
+        for (lc, rc) in self.on.iter() { // by NAME, first match (:134-136)
+            lks.push(self.left.schema().index_of(&lc.name)? as i32);
+            rks.push(self.right.schema().index_of(&rc.name)? as i32);
+        }
+        let mut jt = std::ptr::null_mut();
+        self.ctx.check(unsafe { nqe_hash_join_build_keys(self.ctx.0, single.table.0, lks.as_ptr(), lks.len() as i32, &mut jt) })?;
+        let jt = GpuJoinTable(jt);
+        let mut mk = std::ptr::null_mut();
+        if build_side { self.ctx.check(unsafe { nqe_join_marks_create(self.ctx.0, jt.0, &mut mk) })?; }
+        let marks = GpuJoinMarks(mk); // (a null handle is released as a no-op)
+        let null_flag = if self.null_key_unmatched { NQE_SEMI_NULL_KEY_UNMATCHED } else { 0 };
+        let mut out = vec![];
+        for b in right.iter() {
+            if build_side { // the mark-only pass: no output batch
+                self.ctx.check(unsafe { nqe_hash_join_probe_semi(self.ctx.0, jt.0, b.table.0, rks.as_ptr(), rks.len() as i32, null_flag, marks.0, std::ptr::null_mut()) })?;
+                continue;
+            }
+            let flags = null_flag | if anti { NQE_SEMI_ANTI } else { 0 };
+            let mut t = std::ptr::null_mut();
+            self.ctx.check(unsafe { nqe_hash_join_probe_semi(self.ctx.0, jt.0, b.table.0, rks.as_ptr(), rks.len() as i32, flags, std::ptr::null_mut(), &mut t) })?;
+            out.push(GpuBatch::wrap(t));
+        }
+        if build_side {
+            let mut t = std::ptr::null_mut();
+            self.ctx.check(unsafe { nqe_hash_join_marked_build(self.ctx.0, jt.0, marks.0, if anti { NQE_SEMI_ANTI } else { 0 }, &mut t) })?;
+            out.push(GpuBatch::wrap(t));
+        }
+        drop(marks); // before the join table it is bound to
+        Ok(out)
+    }
+}
+impl PhysicalPlan for GpuHashSemiJoin {
     fn schema(&self) -> &NaiveSchema { &self.schema }
     fn children(&self) -> Result<Vec<PhysicalPlanRef>> { Ok(vec![self.left.clone(), self.right.clone()]) }
     fn execute(&self) -> Result<Vec<RecordBatch>> { self.ctx.download_all(&self.execute_device()?, &self.schema) }

@@ -29,7 +29,7 @@ SYMBOLS = [
     "nqe_filter", "nqe_selection_execute", "nqe_projection_execute", "nqe_selection_projection_execute",
     "nqe_aggregate_execute", "nqe_aggregate_partial", "nqe_aggregate_merge", "nqe_aggregate_merge_packed", "nqe_group_aggregate_execute", "nqe_hash_join_execute",
     "nqe_hash_join_build", "nqe_hash_join_probe", "nqe_join_table_release", "nqe_join_marks_create", "nqe_join_marks_release",
-    "nqe_hash_join_probe_outer", "nqe_hash_join_unmatched_build", "nqe_hash_join_build_keys", "nqe_hash_join_probe_keys", "nqe_hash_join_execute_keys", "nqe_cross_join_execute", "nqe_nested_loop_join_execute", "nqe_sort_execute", "nqe_take", "nqe_synth_fill",
+    "nqe_hash_join_probe_outer", "nqe_hash_join_unmatched_build", "nqe_hash_join_build_keys", "nqe_hash_join_probe_keys", "nqe_hash_join_execute_keys", "nqe_hash_join_probe_semi", "nqe_hash_join_marked_build", "nqe_cross_join_execute", "nqe_nested_loop_join_execute", "nqe_sort_execute", "nqe_take", "nqe_synth_fill",
     "nqe_device_alloc", "nqe_device_free",
     "nqe_comm_get_unique_id", "nqe_comm_rccl_version", "nqe_comm_create", "nqe_comm_create_custom", "nqe_comm_create_p2p", "nqe_comm_destroy", "nqe_comm_rank",
     "nqe_comm_world", "nqe_table_all_gather", "nqe_sharded_aggregate_execute", "nqe_sharded_hash_join_probe",
@@ -144,6 +144,8 @@ def lib():
         "nqe_hash_join_build_keys": (i32, [vp, vp, C.POINTER(i32), i32, pvp]),
         "nqe_hash_join_probe_keys": (i32, [vp, vp, vp, C.POINTER(i32), i32, C.c_uint32, vp, pvp]),
         "nqe_hash_join_execute_keys": (i32, [vp, vp, vp, C.POINTER(i32), C.POINTER(i32), i32, pvp]),
+        "nqe_hash_join_probe_semi": (i32, [vp, vp, vp, C.POINTER(i32), i32, C.c_uint32, vp, pvp]),
+        "nqe_hash_join_marked_build": (i32, [vp, vp, vp, C.c_uint32, pvp]),
         "nqe_cross_join_execute": (i32, [vp, vp, vp, pvp]),
         "nqe_nested_loop_join_execute": (i32, [vp, vp, vp, i32, i32, pvp]),
         "nqe_sort_execute": (i32, [vp, vp, C.POINTER(NqeSortKey), i32, i64, pvp]),
@@ -177,6 +179,8 @@ def lib():
 TABLE_IMMUTABLE = 1  # NQE_TABLE_IMMUTABLE
 MAX_GROUP_KEYS = 8   # NQE_MAX_GROUP_KEYS
 JOIN_KEEP_PROBE = 1  # NQE_JOIN_KEEP_PROBE
+SEMI_ANTI = 1  # NQE_SEMI_ANTI
+SEMI_NULL_KEY_UNMATCHED = 2  # NQE_SEMI_NULL_KEY_UNMATCHED
 
 
 class Context:
@@ -457,6 +461,26 @@ class Context:
         h = C.c_void_p()
         self.check(lib().nqe_hash_join_execute_keys(self.handle, left.handle, right.handle, self._key_array(left_keys), self._key_array(right_keys), len(left_keys), C.byref(h)))
         return Table(self, h, derived_from=(right,))
+
+    def hash_join_probe_semi(self, jt: "JoinTable", right: "Table", right_keys: Sequence[int], anti: bool = False, null_key_unmatched: bool = False,
+                             marks: Optional["JoinMarks"] = None, want_out: bool = True, flags: Optional[int] = None) -> Optional["Table"]:
+        """nqe_hash_join_probe_semi (quirk Q22): the rows of `right` that have (`anti`: do not have) a match in `jt`, every right column
+        and nothing else, in probe order; `marks` records the build rows that matched; `want_out` False is the mark-only pass (returns
+        None).  `flags`: the raw flag word instead of the two booleans"""
+        if flags is None:
+            flags = (SEMI_ANTI if anti else 0) | (SEMI_NULL_KEY_UNMATCHED if null_key_unmatched else 0)
+        h = C.c_void_p()
+        self.check(lib().nqe_hash_join_probe_semi(self.handle, jt.handle, right.handle, self._key_array(right_keys), len(right_keys), flags,
+                                                  marks.handle if marks is not None else None, C.byref(h) if want_out else None))
+        return Table(self, h) if want_out else None
+
+    def hash_join_marked_build(self, jt: "JoinTable", marks: Optional["JoinMarks"], anti: bool = False, flags: Optional[int] = None) -> "Table":
+        """nqe_hash_join_marked_build: the build rows that `marks` has seen match (`anti`: has not), in ascending build row, the visible
+        left columns only"""
+        h = C.c_void_p()
+        self.check(lib().nqe_hash_join_marked_build(self.handle, jt.handle, marks.handle if marks is not None else None,
+                                                    (SEMI_ANTI if anti else 0) if flags is None else flags, C.byref(h)))
+        return Table(self, h)
 
     def cross_join(self, left: "Table", right: "Table") -> "Table":
         """CrossJoin::execute for one batch pair (quirk Q15): left[j % L] beside right[j % R] for j < L*R, no validity"""

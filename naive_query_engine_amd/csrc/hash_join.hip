@@ -28,11 +28,12 @@
 //   build_sorted         (duplicate keys, or an empty build side): perm, slots/cap/shift, direct = no duplicates after all;
 //                        build_sorted_dense adds dense (+ ustart, or the payload fields above when unique); sorted_cols for
 //                        duplicates → probe_duplicates (direct: probe_unique / probe_dense_payload as above)
+// (the semi / anti probe, quirk Q22, reads the same fields for existence alone: its map from build form to existence form is at probe_semi)
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 
-#include "hash_join_outer_kernels.hpp" // (and through it hash_join_probe_kernels.hpp, hash_join_build_kernels.hpp, hash_join_table.hpp)
+#include "hash_join_semi_kernels.hpp" // (and through it hash_join_outer_kernels.hpp, hash_join_probe_kernels.hpp, hash_join_build_kernels.hpp, hash_join_table.hpp)
 
 // which build rows have matched so far (quirk Q19): bit `start` per matched key, left_rows bits in 32-bit words, bound to one join table
 struct nqe_join_marks {
@@ -983,7 +984,7 @@ std::unique_ptr<nqe_table> probe_duplicates(nqe_ctx *ctx, const nqe_join_table *
 // scan, output-driven write pass (outer_write_kernel), and for the build-preserving side a pass over the build rows
 // (unmatched_build_kernel) + compaction.  The match relation is the inner join's, Q11 included.
 // exact null counts of the nullable columns of `out` (count_set_bits_kernel per column, one read-back for all of them)
-void count_nulls_exact(nqe_ctx *ctx, nqe_table *out) {
+void count_nulls_exact(nqe_ctx *ctx, nqe_table *out, const char *label = "join_outer_null_count") {
     std::vector<size_t> which;
     for (size_t c = 0; c < out->cols.size(); ++c)
         if (out->cols[c].validity && out->cols[c].null_count < 0) which.push_back(c);
@@ -994,7 +995,7 @@ void count_nulls_exact(nqe_ctx *ctx, nqe_table *out) {
     }
     BufRef set = dev_alloc_zero(ctx, which.size() * 8);
     for (size_t k = 0; k < which.size(); ++k)
-        launch(ctx, "join_outer_null_count", count_set_bits_kernel, dim3(stream_grid(ctx, (out->rows + 63) / 64, 256)), dim3(256), 0,
+        launch(ctx, label, count_set_bits_kernel, dim3(stream_grid(ctx, (out->rows + 63) / 64, 256)), dim3(256), 0,
                (const uint64_t *)out->cols[which[k]].validity->ptr, out->rows, (unsigned long long *)set->ptr + k);
     std::vector<unsigned long long> h(which.size());
     NQE_HIP_CHECK(hipMemcpyAsync(h.data(), set->ptr, which.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -1189,6 +1190,131 @@ std::unique_ptr<nqe_table> unmatched_build(nqe_ctx *ctx, const nqe_join_table *j
     return out;
 }
 
+// ---- semi and anti joins (quirk Q22): which probe rows have a partner (SEMI) or none (ANTI), and the same question for the build rows
+// through the marks.  One keep-mask pass (semi_keep_kernel) and the selection's compaction over the caller's own columns: no build
+// column is read or written, no per-row word exists.  The existence form follows the build form (the map at the top of this file):
+//   build_unique_dense with dense_full                      → RANGE  (a comparison, no memory access beyond the key)
+//   build_unique_dense / build_sorted_dense with `presence` → BITMAP (one bit per key)
+//   other dense tables (no payload copies, duplicate keys), and every pass over a dense table that marks → LOOKUP (dense[d] != 0; with marks lookup_meta)
+//   hashed tables, wave-cooperatively (semi_keep_coop_kernel): the packed {key, payload} words where the build made them → PACKED, its
+//   16-byte pairs → PAIRS, else — and for every pass that marks — the {key, meta} slots → COOP.  NQE_SEMI_NO_COOP=1 (a diagnostic switch,
+//   read per call) sends hashed tables through LOOKUP's per-lane probe_one instead: same result (profiles/semi_join has the A/B).
+template <int FORM, bool NULLS, bool MARKS> void launch_semi_keep(nqe_ctx *ctx, const char *label, bool anti, bool want_out, dim3 grid, const uint64_t *rk, int64_t n, int64_t ntiles,
+                                                                 const Lookup &L, const uint32_t *presence, const SemiValid &sv, uint32_t *marks, uint64_t *keep, uint32_t *counts) {
+    if constexpr (MARKS) {
+        if (!want_out) return launch(ctx, label, semi_keep_kernel<FORM, false, NULLS, true, false>, grid, dim3(256), 0, rk, n, ntiles, L, presence, sv, marks, keep, counts);
+    }
+    if (anti) launch(ctx, label, semi_keep_kernel<FORM, true, NULLS, MARKS, true>, grid, dim3(256), 0, rk, n, ntiles, L, presence, sv, marks, keep, counts);
+    else launch(ctx, label, semi_keep_kernel<FORM, false, NULLS, MARKS, true>, grid, dim3(256), 0, rk, n, ntiles, L, presence, sv, marks, keep, counts);
+}
+template <int TABLE, bool NULLS, bool MARKS> void launch_semi_coop(nqe_ctx *ctx, const char *label, bool anti, bool want_out, dim3 grid, const uint64_t *rk, int64_t n, int64_t ntiles,
+                                                                  const SemiHashed &H, const SemiValid &sv, uint32_t *marks, uint64_t *keep, uint32_t *counts) {
+    if constexpr (MARKS) {
+        if (!want_out) return launch(ctx, label, semi_keep_coop_kernel<TABLE, false, NULLS, true, false>, grid, dim3(256), 0, rk, n, ntiles, H, sv, marks, keep, counts);
+    }
+    if (anti) launch(ctx, label, semi_keep_coop_kernel<TABLE, true, NULLS, MARKS, true>, grid, dim3(256), 0, rk, n, ntiles, H, sv, marks, keep, counts);
+    else launch(ctx, label, semi_keep_coop_kernel<TABLE, false, NULLS, MARKS, true>, grid, dim3(256), 0, rk, n, ntiles, H, sv, marks, keep, counts);
+}
+// `right_with_key`: the caller's columns (the first `out_cols`) and, as its last column, the key to look up — the key column itself, or
+// the code column of a join on several keys.  `key_valid`: the validity bitmaps of the probe key columns when NULL keys match nothing
+// (null otherwise).  Returns null for the mark-only pass (`want_out` false).
+std::unique_ptr<nqe_table> probe_semi(nqe_ctx *ctx, const nqe_join_table *jt, const nqe_table *right_with_key, size_t out_cols, bool anti, const SemiValid *key_valid,
+                                      uint32_t *marks, bool want_out) {
+    const DevColumn &rk_orig = right_with_key->cols.back();
+    DevColumn rk_codes;
+    if (rk_orig.dtype == NQE_UTF8) rk_codes = utf8_encode_probe(ctx, rk_orig, jt->dict);
+    const DevColumn &rk = rk_orig.dtype == NQE_UTF8 ? rk_codes : rk_orig;
+    const int64_t n = right_with_key->rows;
+    BufRef counts;
+    KeepMask km;
+    if (want_out) km = new_keep_mask(ctx, n, &counts);
+    const int64_t ntiles = (n + TILE_ROWS - 1) / TILE_ROWS;
+    SemiValid sv;
+    std::memset(&sv, 0, sizeof(sv));
+    bool nulls = false;
+    if (key_valid)
+        for (int j = 0; j < NQE_MAX_JOIN_KEYS; ++j) {
+            sv.v[j] = key_valid->v[j];
+            nulls = nulls || sv.v[j] != nullptr;
+        }
+    const bool hashed = !jt->dense && getenv("NQE_SEMI_NO_COOP") == nullptr;
+    const int table = (marks || !jt->slotsp) ? SEMI_SLOTS : (jt->pp.pbits ? SEMI_PACKED : SEMI_PAIRS);
+    const int form = hashed ? -1 : (marks ? SEMI_LOOKUP : (jt->dense_full ? SEMI_RANGE : (jt->presence ? SEMI_BITMAP : SEMI_LOOKUP)));
+    const char *label = hashed ? (table == SEMI_SLOTS ? "join_semi_keep_coop" : (table == SEMI_PACKED ? "join_semi_keep_packed" : "join_semi_keep_pairs"))
+                               : (form == SEMI_RANGE ? "join_semi_keep_range" : (form == SEMI_BITMAP ? "join_semi_keep_bitmap" : "join_semi_keep_lookup"));
+    if (getenv("NQE_DEBUG"))
+        fprintf(stderr, "[nqe] join semi: n=%lld %s anti=%d nulls=%d marks=%d out=%d\n", (long long)n, label, int(anti), int(nulls), int(marks != nullptr), int(want_out));
+    if (ntiles) {
+        const dim3 grid(stream_grid(ctx, ntiles, 4));
+        const Lookup L = lookup_of(jt);
+        const uint32_t *pp = jt->presence ? (const uint32_t *)jt->presence->ptr : (const uint32_t *)nullptr;
+        uint64_t *kp = want_out ? (uint64_t *)km.keep->ptr : (uint64_t *)nullptr;
+        uint32_t *cp = want_out ? (uint32_t *)counts->ptr : (uint32_t *)nullptr;
+        SemiHashed H;
+        std::memset(&H, 0, sizeof(H));
+        if (hashed) { // (a dense table built without sorting has no hash table at all)
+            H.tab = (const ulonglong2 *)(table == SEMI_SLOTS ? jt->slots->ptr : jt->slotsp->ptr);
+            H.cap = jt->cap;
+            H.shift = jt->shift;
+            H.filler = jt->filler;
+            H.pp = jt->pp;
+        }
+#define NQE_SEMI(FORM, MARKS)                                                                                                                   \
+    (nulls ? launch_semi_keep<FORM, true, MARKS>(ctx, label, anti, want_out, grid, rk.words(), n, ntiles, L, pp, sv, marks, kp, cp)             \
+           : launch_semi_keep<FORM, false, MARKS>(ctx, label, anti, want_out, grid, rk.words(), n, ntiles, L, pp, sv, marks, kp, cp))
+#define NQE_SEMI_COOP(TABLE, MARKS)                                                                                                             \
+    (nulls ? launch_semi_coop<TABLE, true, MARKS>(ctx, label, anti, want_out, grid, rk.words(), n, ntiles, H, sv, marks, kp, cp)                \
+           : launch_semi_coop<TABLE, false, MARKS>(ctx, label, anti, want_out, grid, rk.words(), n, ntiles, H, sv, marks, kp, cp))
+        if (hashed && marks) NQE_SEMI_COOP(SEMI_SLOTS, true);
+        else if (hashed && table == SEMI_SLOTS) NQE_SEMI_COOP(SEMI_SLOTS, false);
+        else if (hashed && table == SEMI_PACKED) NQE_SEMI_COOP(SEMI_PACKED, false);
+        else if (hashed) NQE_SEMI_COOP(SEMI_PAIRS, false);
+        else if (marks) NQE_SEMI(SEMI_LOOKUP, true);
+        else if (form == SEMI_RANGE) NQE_SEMI(SEMI_RANGE, false);
+        else if (form == SEMI_BITMAP) NQE_SEMI(SEMI_BITMAP, false);
+        else NQE_SEMI(SEMI_LOOKUP, false);
+#undef NQE_SEMI
+#undef NQE_SEMI_COOP
+    }
+    if (!want_out) {
+        sync(ctx); // the probe codes are released on return
+        return nullptr;
+    }
+    km = finish_mask(ctx, km, counts);
+    auto out = std::make_unique<nqe_table>();
+    out->ctx = ctx;
+    out->rows = km.total;
+    for (size_t c = 0; c < out_cols; ++c) out->cols.push_back(compact_column(ctx, right_with_key->cols[c], km));
+    count_nulls_exact(ctx, out.get(), "join_semi_null_count");
+    sync(ctx);
+    return out;
+}
+// the build rows whose bit is set (anti: not set), in ascending build row: the visible left columns and nothing else
+std::unique_ptr<nqe_table> marked_build(nqe_ctx *ctx, const nqe_join_table *jt, const uint32_t *marks, bool anti) {
+    const int64_t n = jt->left_rows;
+    DevColumn codes;
+    const uint64_t *bkeys = nullptr;
+    if (!jt->direct) { // duplicate keys: the row's own key finds the bit its key group shares
+        const DevColumn &kc = jt->left_cols[size_t(jt->left_key)];
+        if (kc.dtype == NQE_UTF8) codes = utf8_encode_probe(ctx, kc, jt->dict);
+        bkeys = kc.dtype == NQE_UTF8 ? codes.words() : kc.words();
+    }
+    BufRef counts;
+    KeepMask km = new_keep_mask(ctx, n, &counts);
+    if (km.ntiles)
+        launch(ctx, "join_semi_marked", anti ? marked_build_kernel<true> : marked_build_kernel<false>, dim3(stream_grid(ctx, km.ntiles, 4)), dim3(256), 0, bkeys, n, km.ntiles, lookup_of(jt),
+               marks, (uint64_t *)km.keep->ptr, (uint32_t *)counts->ptr);
+    km = finish_mask(ctx, km, counts);
+    auto out = std::make_unique<nqe_table>();
+    out->ctx = ctx;
+    out->rows = km.total;
+    const size_t visible = jt->left_cols.size() - (jt->keys ? 1 : 0); // (never the hidden code column of a join on several keys)
+    for (size_t c = 0; c < visible; ++c) out->cols.push_back(compact_column(ctx, jt->left_cols[c], km));
+    count_nulls_exact(ctx, out.get(), "join_semi_null_count");
+    sync(ctx);
+    return out;
+}
+
 std::unique_ptr<nqe_table> probe_table(nqe_ctx *ctx, const nqe_join_table *jt, const nqe_table *right, int right_key) {
     if (right_key < 0 || size_t(right_key) >= right->cols.size()) fail(NQE_ERR_LOGICAL, "ColumnExpr must has name or idx");
     const DevColumn &rk_orig = right->cols[size_t(right_key)];
@@ -1213,6 +1339,9 @@ void check_outer_args(nqe_ctx *ctx, const nqe_join_table *build, uint32_t flags,
     if (marks && (marks->ctx != ctx || marks->table != build || marks->rows != build->left_rows))
         fail(NQE_ERR_INVALID_ARGUMENT, "nqe_hash_join_probe_outer: the marks belong to another join table or context");
 }
+bool foreign_marks(nqe_ctx *ctx, const nqe_join_table *build, const nqe_join_marks *marks) {
+    return marks->ctx != ctx || marks->table != build || marks->rows != build->left_rows;
+}
 
 } // namespace
 
@@ -1232,6 +1361,21 @@ nqe_table *join_probe_coded(nqe_ctx *ctx, const nqe_join_table *jt, const nqe_ta
     flags_reset(ctx);
     if (flags == 0 && !marks) return probe_table(ctx, jt, right_with_code, key).release();
     return probe_outer(ctx, jt, right_with_code, key, (flags & NQE_JOIN_KEEP_PROBE) != 0, marks ? (uint32_t *)marks->bits->ptr : (uint32_t *)nullptr).release();
+}
+void join_check_semi_args(nqe_ctx *ctx, const nqe_join_table *jt, uint32_t flags, const nqe_join_marks *marks) {
+    if (flags & ~(NQE_SEMI_ANTI | NQE_SEMI_NULL_KEY_UNMATCHED)) fail(NQE_ERR_INVALID_ARGUMENT, "nqe_hash_join_probe_semi: unknown flag bits");
+    if (marks && foreign_marks(ctx, jt, marks)) fail(NQE_ERR_INVALID_ARGUMENT, "nqe_hash_join_probe_semi: the marks belong to another join table or context");
+}
+const DevColumn &join_table_key_column(const nqe_join_table *jt) { return jt->left_cols[size_t(jt->left_key)]; }
+nqe_table *join_semi_coded(nqe_ctx *ctx, const nqe_join_table *jt, const nqe_table *right_with_key, size_t out_cols, uint32_t flags, const uint8_t *const *key_valid,
+                           nqe_join_marks *marks, bool want_out) {
+    SemiValid sv;
+    std::memset(&sv, 0, sizeof(sv));
+    if (key_valid)
+        for (int j = 0; j < NQE_MAX_JOIN_KEYS; ++j) sv.v[j] = key_valid[j];
+    flags_reset(ctx);
+    return probe_semi(ctx, jt, right_with_key, out_cols, (flags & NQE_SEMI_ANTI) != 0, key_valid ? &sv : nullptr, marks ? (uint32_t *)marks->bits->ptr : (uint32_t *)nullptr, want_out)
+        .release();
 }
 
 } // namespace nqe
@@ -1305,6 +1449,17 @@ nqe_status nqe_hash_join_unmatched_build(nqe_ctx *ctx, const nqe_join_table *bui
     }
     flags_reset(ctx);
     *out = unmatched_build(ctx, build, (const uint32_t *)marks->bits->ptr, right_dtypes, num_right).release();
+    NQE_API_END()
+}
+
+nqe_status nqe_hash_join_marked_build(nqe_ctx *ctx, const nqe_join_table *build, const nqe_join_marks *marks, uint32_t flags, nqe_table **out) {
+    NQE_API_BEGIN(ctx)
+    if (!ctx || !build || !out) fail(NQE_ERR_INVALID_ARGUMENT, "bad arguments");
+    if (!marks) fail(NQE_ERR_INVALID_ARGUMENT, "nqe_hash_join_marked_build: marks are required");
+    if (flags & ~NQE_SEMI_ANTI) fail(NQE_ERR_INVALID_ARGUMENT, "nqe_hash_join_marked_build: unknown flag bits");
+    if (foreign_marks(ctx, build, marks)) fail(NQE_ERR_INVALID_ARGUMENT, "nqe_hash_join_marked_build: the marks belong to another join table or context");
+    flags_reset(ctx);
+    *out = marked_build(ctx, build, (const uint32_t *)marks->bits->ptr, (flags & NQE_SEMI_ANTI) != 0).release();
     NQE_API_END()
 }
 

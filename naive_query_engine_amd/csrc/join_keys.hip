@@ -13,8 +13,13 @@
 //                    an all-integer tuple here too: same result): build: group_keys_dict, code = representative build row, the slot
 //                    table stays alive in the join table;  probe: join_keys_lookup, find-only over that table.
 //
-// No validity buffer is read anywhere: the hash join compares raw slots (quirk Q11), at every key position.  An EMPTY build side takes
-// the packed path with spans of 0 (integer pairs) or an empty dictionary (a Utf8 pair): every probe row gets JOIN_KEYS_NO_MATCH.
+// The semi / anti probe (quirk Q22, nqe_hash_join_probe_semi: one door for tables built on one key and on several) composes the same way:
+// the probe codes — or the one key column again — ride as the last column into hash_join.hip's probe_semi, which compacts the caller's
+// columns alone.
+//
+// No validity buffer is read anywhere (the semi probe's NQE_SEMI_NULL_KEY_UNMATCHED apart): the hash join compares raw slots (quirk
+// Q11), at every key position.  An EMPTY build side takes the packed path with spans of 0 (integer pairs) or an empty dictionary (a
+// Utf8 pair): every probe row gets JOIN_KEYS_NO_MATCH.
 #include <cstdlib>
 #include <memory>
 #include <string>
@@ -171,6 +176,25 @@ nqe_table *probe_keys(nqe_ctx *ctx, const nqe_join_table *jt, const JoinKeysStat
     return out.release();
 }
 
+// the semi / anti probe (quirk Q22): the caller's columns + the key to look up as the last column — the probe codes of a tuple, or the
+// one key column again (an alias, not a copy).  The compaction loops over the caller's columns only: the code column never exists in
+// the output.  `st` null: a table built on one key
+nqe_table *probe_semi_keys(nqe_ctx *ctx, const nqe_join_table *jt, const JoinKeysState *st, const nqe_table *right, const int32_t *right_keys, int32_t k, uint32_t flags,
+                           nqe_join_marks *marks, bool want_out) {
+    std::vector<DevColumn> keys;
+    const uint8_t *valid[NQE_MAX_JOIN_KEYS] = {};
+    for (int i = 0; i < k; ++i) {
+        keys.push_back(right->cols[size_t(right_keys[i])]);
+        valid[i] = keys.back().valid();
+    }
+    nqe_table with_key;
+    with_key.ctx = ctx;
+    with_key.rows = right->rows;
+    with_key.cols = right->cols;
+    with_key.cols.push_back(st ? probe_codes(ctx, *st, keys, right->rows) : keys[0]);
+    return join_semi_coded(ctx, jt, &with_key, right->cols.size(), flags, (flags & NQE_SEMI_NULL_KEY_UNMATCHED) ? valid : nullptr, marks, want_out);
+}
+
 void check_status(nqe_ctx *ctx, nqe_status st) {
     if (st != NQE_OK) fail(st, ctx->last_error);
 }
@@ -210,6 +234,29 @@ nqe_status nqe_hash_join_probe_keys(nqe_ctx *ctx, const nqe_join_table *build, c
         check_probe_keys(dtypes, join_table_columns(build) - 1, right, right_keys, num_keys);
         *out = probe_keys(ctx, build, *st, right, right_keys, flags, marks);
     }
+    NQE_API_END()
+}
+
+nqe_status nqe_hash_join_probe_semi(nqe_ctx *ctx, const nqe_join_table *build, const nqe_table *right, const int32_t *right_keys, int32_t num_keys, uint32_t flags,
+                                    nqe_join_marks *marks, nqe_table **out) {
+    NQE_API_BEGIN(ctx)
+    if (!ctx || !build || !right || !right_keys) fail(NQE_ERR_INVALID_ARGUMENT, "bad arguments");
+    if (!out && !marks) fail(NQE_ERR_INVALID_ARGUMENT, "nqe_hash_join_probe_semi: neither an output nor marks");
+    check_key_count(num_keys);
+    const JoinKeysState *st = join_table_keys(build);
+    if (num_keys != (st ? st->k : 1)) fail(NQE_ERR_INVALID_ARGUMENT, "nqe_hash_join_probe_semi: the join table was built on " + std::to_string(st ? st->k : 1) + " key(s)");
+    join_check_semi_args(ctx, build, flags, marks);
+    // (no column limit: the columns are compacted one at a time and no build column is written)
+    const DevColumn *build_keys[NQE_MAX_JOIN_KEYS];
+    for (int i = 0; i < num_keys; ++i) build_keys[i] = st ? &st->build_keys[size_t(i)] : &join_table_key_column(build);
+    for (int i = 0; i < num_keys; ++i) key_column(right, right_keys[i]);
+    for (int i = 0; i < num_keys; ++i) join_check_key_types(build_keys[i]->dtype, right->cols[size_t(right_keys[i])].dtype);
+    if (flags & NQE_SEMI_NULL_KEY_UNMATCHED)
+        for (int i = 0; i < num_keys; ++i)
+            if (build_keys[i]->validity && build_keys[i]->null_count != 0)
+                fail(NQE_ERR_NOT_SUPPORTED, "nqe_hash_join_probe_semi: NQE_SEMI_NULL_KEY_UNMATCHED over a build key column with NULLs (the table would have to be rebuilt without them)");
+    nqe_table *t = probe_semi_keys(ctx, build, st, right, right_keys, num_keys, flags, marks, out != nullptr);
+    if (out) *out = t;
     NQE_API_END()
 }
 

@@ -34,5 +34,15 @@ size_t join_table_columns(const nqe_join_table *jt);
 void join_check_outer_args(nqe_ctx *ctx, const nqe_join_table *jt, uint32_t flags, const nqe_join_marks *marks);
 // probe_table (flags == 0 and no marks) or probe_outer over `right_with_code`, keyed by its last column
 nqe_table *join_probe_coded(nqe_ctx *ctx, const nqe_join_table *jt, const nqe_table *right_with_code, uint32_t flags, nqe_join_marks *marks);
+// ---- semi and anti joins (quirk Q22)
+// the flag and marks checks of nqe_hash_join_probe_semi; launches nothing
+void join_check_semi_args(nqe_ctx *ctx, const nqe_join_table *jt, uint32_t flags, const nqe_join_marks *marks);
+// the column the table is keyed by (the hidden code column of a table built on several keys)
+const DevColumn &join_table_key_column(const nqe_join_table *jt);
+// probe_semi over `right_with_key`: its last column is the key to look up (the key column again, or the code column), its first
+// `out_cols` columns are compacted into the result.  `key_valid`: NQE_MAX_JOIN_KEYS validity bitmaps of the probe key columns (null
+// entries: all valid) when NULL keys match nothing, else null.  `want_out` false: the mark-only pass, returns null
+nqe_table *join_semi_coded(nqe_ctx *ctx, const nqe_join_table *jt, const nqe_table *right_with_key, size_t out_cols, uint32_t flags, const uint8_t *const *key_valid,
+                           nqe_join_marks *marks, bool want_out);
 
 } // namespace nqe

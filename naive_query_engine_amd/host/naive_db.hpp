@@ -858,6 +858,77 @@ struct MultiKeyHashJoin : PhysicalPlan {
     }
 };
 
+// ---------------------------------------------------------------- semi and anti hash joins (no reference file: JoinType is {Inner, Left, Right, Cross}, plan.rs:134-139)
+// Quirk Q22: which rows of one child have a partner in the other — WHERE k IN (SELECT ...), EXISTS, NOT EXISTS.  The match relation is
+// MultiKeyHashJoin's, Q11 included (LEFT child = build side, RIGHT = probe side, every pair by NAME, key validity ignored at every position)
+// — unless null_key_unmatched: then a probe row with a NULL at any key position matches nothing.  ProbeSemi / ProbeAnti: one output batch
+// per probe batch with the right columns alone, the probe rows that have a match / none, each once, in probe order.  BuildSemi / BuildAnti:
+// one final batch, always emitted, possibly with 0 rows, of the left columns alone: the build rows that matched in some probe batch / in
+// none, in ascending build row.  schema() is the kept side's schema.  Nothing is kept between execute() calls.
+enum class SemiJoinType { ProbeSemi, ProbeAnti, BuildSemi, BuildAnti };
+struct HashSemiJoin : PhysicalPlan {
+    PhysicalPlanRef left, right;
+    std::vector<std::pair<Column, Column>> on;
+    SemiJoinType semi_type = SemiJoinType::ProbeSemi;
+    NaiveSchema schema_;
+    bool null_key_unmatched = false;
+    static PhysicalPlanRef create(PhysicalPlanRef left, PhysicalPlanRef right, std::vector<std::pair<Column, Column>> on, SemiJoinType st, NaiveSchema schema,
+                                  bool null_key_unmatched = false) {
+        auto p = std::make_shared<HashSemiJoin>();
+        p->left = std::move(left); p->right = std::move(right); p->on = std::move(on); p->semi_type = st; p->schema_ = std::move(schema);
+        p->null_key_unmatched = null_key_unmatched;
+        return p;
+    }
+    const NaiveSchema &schema() const override { return schema_; }
+    std::vector<PhysicalPlanRef> children() const override { return {left, right}; }
+    std::vector<RecordBatch> execute() override {
+        std::vector<RecordBatch> lb = left->execute(), rb = right->execute();
+        if (on.empty()) throw ErrorCode(ErrorCode::PlanError, "Inner Join on Conditions can't not be empty");
+        if (lb.empty()) throw ErrorCode(ErrorCode::NotSupported, "join with an empty left batch list is not supported on the device path");
+        const ContextRef &ctx = lb[0].ctx();
+        std::shared_ptr<nqe_table> single;
+        nqe_table *ltab = lb[0].raw();
+        if (lb.size() > 1) { // concat_batches (:132)
+            std::vector<const nqe_table *> parts;
+            for (auto &b : lb) parts.push_back(b.raw());
+            nqe_table *c = nullptr;
+            ctx->check(nqe_table_concat(ctx->raw(), parts.data(), int32_t(parts.size()), &c));
+            single.reset(c, [](nqe_table *p) { nqe_table_release(p); });
+            ltab = c;
+        }
+        std::vector<int32_t> lkeys, rkeys;
+        for (auto &p : on) lkeys.push_back(int32_t(ColumnExpr::try_create(p.first.name, std::nullopt)->resolve(lb[0].schema()))); // by NAME (:134-136)
+        nqe_join_table *jt = nullptr;
+        ctx->check(nqe_hash_join_build_keys(ctx->raw(), ltab, lkeys.data(), int32_t(lkeys.size()), &jt));
+        std::shared_ptr<nqe_join_table> jguard(jt, [](nqe_join_table *p) { nqe_join_table_release(p); });
+        const bool build_side = semi_type == SemiJoinType::BuildSemi || semi_type == SemiJoinType::BuildAnti;
+        const bool anti = semi_type == SemiJoinType::ProbeAnti || semi_type == SemiJoinType::BuildAnti;
+        nqe_join_marks *marks = nullptr;
+        if (build_side) ctx->check(nqe_join_marks_create(ctx->raw(), jt, &marks));
+        std::shared_ptr<nqe_join_marks> mguard(marks, [](nqe_join_marks *p) { nqe_join_marks_release(p); });
+        const uint32_t null_flag = null_key_unmatched ? NQE_SEMI_NULL_KEY_UNMATCHED : 0u;
+        auto kept = [&](const NaiveSchema &side, nqe_table *t) { return int32_t(schema_.fields().size()) == nqe_table_num_columns(t) ? schema_ : side; };
+        std::vector<RecordBatch> out;
+        for (auto &b : rb) {
+            rkeys.clear();
+            for (auto &p : on) rkeys.push_back(int32_t(ColumnExpr::try_create(p.second.name, std::nullopt)->resolve(b.schema())));
+            if (build_side) { // the mark-only pass: no output batch
+                ctx->check(nqe_hash_join_probe_semi(ctx->raw(), jt, b.raw(), rkeys.data(), int32_t(rkeys.size()), null_flag, marks, nullptr));
+                continue;
+            }
+            nqe_table *t = nullptr;
+            ctx->check(nqe_hash_join_probe_semi(ctx->raw(), jt, b.raw(), rkeys.data(), int32_t(rkeys.size()), null_flag | (anti ? NQE_SEMI_ANTI : 0u), nullptr, &t));
+            out.push_back(b.with_table(kept(b.schema(), t), t));
+        }
+        if (build_side) {
+            nqe_table *t = nullptr;
+            ctx->check(nqe_hash_join_marked_build(ctx->raw(), jt, marks, anti ? NQE_SEMI_ANTI : 0u, &t));
+            out.push_back(lb[0].with_table(kept(lb[0].schema(), t), t));
+        }
+        return out;
+    }
+};
+
 // ---------------------------------------------------------------- physical_plan/cross_join.rs:26-192
 // One output batch per (outer, inner) batch pair, outer-major.  Quirk Q15: output row j takes left row j % L and right row j % R
 // (a Cartesian product only when gcd(L, R) = 1); no output column has a validity bitmap; nothing is kept between execute() calls.
@@ -1149,6 +1220,7 @@ inline PhysicalPlanRef rewrite(const PhysicalPlanRef &plan) {
     if (auto o = std::dynamic_pointer_cast<PhysicalOffsetPlan>(plan)) return PhysicalOffsetPlan::create(rewrite(o->input), o->n);
     if (auto o = std::dynamic_pointer_cast<HashOuterJoin>(plan)) return HashOuterJoin::create(rewrite(o->left), rewrite(o->right), o->on, o->join_type, o->schema_);
     if (auto m = std::dynamic_pointer_cast<MultiKeyHashJoin>(plan)) return MultiKeyHashJoin::create(rewrite(m->left), rewrite(m->right), m->on, m->join_type, m->schema_);
+    if (auto s = std::dynamic_pointer_cast<HashSemiJoin>(plan)) return HashSemiJoin::create(rewrite(s->left), rewrite(s->right), s->on, s->semi_type, s->schema_, s->null_key_unmatched);
     if (auto j = std::dynamic_pointer_cast<HashJoin>(plan)) return HashJoin::create(rewrite(j->left), rewrite(j->right), j->on, j->join_type, j->schema_);
     if (auto c = std::dynamic_pointer_cast<CrossJoin>(plan)) return CrossJoin::create(rewrite(c->left), rewrite(c->right), c->join_type, c->schema_);
     if (auto n = std::dynamic_pointer_cast<NestedLoopJoin>(plan)) return NestedLoopJoin::create(rewrite(n->left), rewrite(n->right), n->on, n->join_type, n->schema_);

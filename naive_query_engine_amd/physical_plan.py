@@ -620,6 +620,66 @@ class MultiKeyHashJoin(PhysicalPlan):
         return out
 
 
+# ----------------------------------------------------------------------------- semi and anti hash joins
+class SemiJoinType:
+    ProbeSemi, ProbeAnti, BuildSemi, BuildAnti = range(4)
+
+
+class HashSemiJoin(PhysicalPlan):
+    """Which rows of one child have a partner in the other (quirk Q22; the reference has no such operator): the join behind
+    WHERE k IN (SELECT ...), EXISTS and NOT EXISTS.  The match relation is MultiKeyHashJoin's, Q11 included: LEFT child = build side,
+    RIGHT = probe side, every `on` pair resolved by NAME, first match (Q12), key validity ignored at every position — unless
+    `null_key_unmatched`: then a probe row with a NULL at any key position matches nothing (a build key column with NULLs is
+    NotSupported).  ProbeSemi / ProbeAnti: one output batch per probe batch with the right columns alone — the probe rows that have
+    a match / have none, each once, in probe order.  BuildSemi / BuildAnti: one final batch, always emitted, possibly with 0 rows, of
+    the left columns alone — the build rows that matched in some probe batch / in none, in ascending build row.  schema() is the kept
+    side's schema.  An empty `on` raises PlanError after both children ran.  Nothing is kept between execute() calls."""
+
+    def __init__(self, left, right, on, semi_type, schema, null_key_unmatched=False):
+        self.left, self.right, self.on, self.semi_type, self._schema = left, right, list(on), semi_type, list(schema)
+        self.null_key_unmatched = bool(null_key_unmatched)
+
+    @staticmethod
+    def create(left: PhysicalPlan, right: PhysicalPlan, on: Sequence[Tuple[ColumnRef, ColumnRef]], semi_type, schema: NaiveSchema,
+               null_key_unmatched: bool = False) -> "HashSemiJoin":
+        return HashSemiJoin(left, right, on, semi_type, schema, null_key_unmatched)
+
+    def schema(self):
+        return self._schema
+
+    def children(self):
+        return [self.left, self.right]
+
+    def execute(self):
+        if self.semi_type not in (SemiJoinType.ProbeSemi, SemiJoinType.ProbeAnti, SemiJoinType.BuildSemi, SemiJoinType.BuildAnti):
+            raise ErrorCode(Status.PlanError, "HashSemiJoin: the semi join type must be ProbeSemi, ProbeAnti, BuildSemi or BuildAnti")
+        lb = self.left.execute()
+        rb = self.right.execute()
+        if not self.on:  # as HashJoin (hash_join.rs:125-129)
+            raise ErrorCode(Status.PlanError, "Inner Join on Conditions can't not be empty")
+        ctx = _ctx_of(lb or rb)
+        if not lb:
+            raise ErrorCode(Status.NotSupported, "join with an empty left batch list is not supported on the device path")
+        ltab = lb[0].table if len(lb) == 1 else ctx.concat([b.table for b in lb])  # concat_batches (:132)
+        lkeys = [ColumnExpr.try_create(l.name, None).resolve(lb[0].fields) for l, _ in self.on]  # by NAME, first match (:134-136)
+        jt = ctx.hash_join_build_keys(ltab, lkeys)
+        build_side = self.semi_type in (SemiJoinType.BuildSemi, SemiJoinType.BuildAnti)
+        anti = self.semi_type in (SemiJoinType.ProbeAnti, SemiJoinType.BuildAnti)
+        marks = ctx.join_marks(jt) if build_side else None
+        out = []
+        for b in rb:
+            rkeys = [ColumnExpr.try_create(r.name, None).resolve(b.fields) for _, r in self.on]
+            if build_side:  # the mark-only pass: no output batch
+                ctx.hash_join_probe_semi(jt, b.table, rkeys, null_key_unmatched=self.null_key_unmatched, marks=marks, want_out=False)
+                continue
+            t = ctx.hash_join_probe_semi(jt, b.table, rkeys, anti=anti, null_key_unmatched=self.null_key_unmatched)
+            out.append(DeviceRecordBatch(self._schema if len(self._schema) == t.num_columns else list(b.fields), t))
+        if build_side:
+            t = ctx.hash_join_marked_build(jt, marks, anti=anti)
+            out.append(DeviceRecordBatch(self._schema if len(self._schema) == t.num_columns else list(lb[0].fields), t))
+        return out
+
+
 # ----------------------------------------------------------------------------- cross join
 class CrossJoin(PhysicalPlan):
     """src/physical_plan/cross_join.rs:26-192 — one output batch per (outer, inner) batch pair, outer-major; quirk Q15: with L and R

@@ -21,7 +21,7 @@ from __future__ import annotations
 from typing import Dict, List, Optional, Sequence
 
 from .arrow_host import ErrorCode, Field, RecordBatch, Status
-from .physical_plan import (CrossJoin, CsvConfig, CsvTable, DeviceRecordBatch, GroupedAggregatePlan, HashJoin, HashOuterJoin, MemTable, MultiKeyHashJoin, NaiveSchema, NestedLoopJoin, PhysicalAggregatePlan, PhysicalLimitPlan,
+from .physical_plan import (CrossJoin, CsvConfig, CsvTable, DeviceRecordBatch, GroupedAggregatePlan, HashJoin, HashOuterJoin, HashSemiJoin, MemTable, MultiKeyHashJoin, NaiveSchema, NestedLoopJoin, PhysicalAggregatePlan, PhysicalLimitPlan,
                             PhysicalOffsetPlan, PhysicalPlan, PhysicalSortPlan, ProjectionPlan, ScanPlan, SelectionPlan, _ctx_of, _Materialized)
 
 
@@ -142,6 +142,8 @@ def rewrite(plan: PhysicalPlan) -> PhysicalPlan:
         return HashOuterJoin.create(rewrite(plan.left), rewrite(plan.right), plan.on, plan.join_type, plan._schema)
     if isinstance(plan, MultiKeyHashJoin):
         return MultiKeyHashJoin.create(rewrite(plan.left), rewrite(plan.right), plan.on, plan.join_type, plan._schema)
+    if isinstance(plan, HashSemiJoin):
+        return HashSemiJoin.create(rewrite(plan.left), rewrite(plan.right), plan.on, plan.semi_type, plan._schema, plan.null_key_unmatched)
     if isinstance(plan, HashJoin):
         return HashJoin.create(rewrite(plan.left), rewrite(plan.right), plan.on, plan.join_type, plan._schema)
     if isinstance(plan, CrossJoin):
