@@ -946,7 +946,10 @@ void AggRun::classify_key() {
     kk = 2, fast_key = -1;
     if (a.key.nops == 0) kk = 0, fast_key = 0;
     else if (a.key.nops == 1 && a.key.op[0] == NQE_OP_MODULOS && !a.key.lit_left[0] &&
-             (a.key.op_dtype[0] == NQE_INT64 || a.key.op_dtype[0] == NQE_UINT64)) {
+             (a.key.op_dtype[0] == NQE_INT64 || a.key.op_dtype[0] == NQE_UINT64) &&
+             // (`col % -1`: |-1| is 2^0, but i64::MIN % -1 raises where the mask form would answer 0 — a key that can fault is left to the
+             // general kernel's checked eval_simple, like `col / -1` and a zero divisor below)
+             !(a.key.op_dtype[0] == NQE_INT64 && a.key.lit[0] == ~0ull)) {
         if (a.key.aux[0].pow2_shift >= 0) kk = 1, fast_key = 1;
         else if (a.key.aux[0].more >= 0) fast_key = 2; // `col % d`, d not a power of two: magic multiply
     }
