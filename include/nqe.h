@@ -735,6 +735,65 @@ typedef struct nqe_sort_key {
 nqe_status nqe_sort_execute(nqe_ctx *ctx, const nqe_table *in, const nqe_sort_key *keys, int32_t num_keys,
                             int64_t fetch /* < 0: all rows */, nqe_table **out);
 
+/* ------------------------------------------------------------------ window functions
+ * f(...) OVER (PARTITION BY ... ORDER BY ...) over ONE table — quirk Q23: the reference has no
+ * window expression at all (logical_plan/expression.rs:22-46), so the definition is this project's.
+ * All functions of one call share one window: the same partition keys and the same order keys.
+ * The sorted order is nqe_sort_execute's order by (the partition keys with default options, then
+ * the order keys as given); the sort is stable, so rows that tie on every key keep their input
+ * order and every function is deterministic, ROW_NUMBER and the ROWS frame among tied rows
+ * included.  Two rows are in the same PARTITION iff they tie on every partition key, ties being
+ * the sort's own: Int64 / UInt64 the 64-bit word, Float64 as OrderedFloat (-0.0 = +0.0, every NaN
+ * equals every NaN), Boolean the bit, Utf8 byte for byte; a NULL equals a NULL, whatever lies under
+ * it, and differs from every value.  Two rows of one partition are PEERS iff they also tie on
+ * every order key.  With no order keys all rows of a partition are peers and ROWS runs in input
+ * order; with no partition keys the table is one partition.
+ * The output is ONE table of num_funcs columns and in->rows rows IN INPUT ORDER: row i holds the
+ * functions' values for input row i.  No column has a validity buffer (null_count 0); the input
+ * columns are not copied.
+ *   ROW_NUMBER, RANK, DENSE_RANK   UInt64, 1-based: RANK = 1 + the partition rows before the row's
+ *                                  first peer, DENSE_RANK = the peer groups up to the row's own
+ *   COUNT, SUM, MIN, MAX, AVG      exactly the aggregates of nqe_aggregate_execute (quirk Q10) over
+ *                                  the rows of the frame: Int64 / UInt64 / Float64 inputs, every
+ *                                  value converted to f64 first, a NULL skipped; COUNT UInt64, the
+ *                                  others Float64; a frame without valid rows gives sum 0.0, avg
+ *                                  NaN, min f64::MAX, max f64::MIN; min ignores NaN, max becomes
+ *                                  NaN when the frame holds one; avg divides by the count as u32
+ * Errors, all before any launch or allocation, in this order: NULL ctx / in / out or a NULL array
+ * with a positive count NQE_ERR_INVALID_ARGUMENT; func, or an aggregate's frame, outside its enum
+ * NQE_ERR_INVALID_ARGUMENT; num_funcs <= 0 NQE_ERR_PLAN; more keys or functions than the limits
+ * NQE_ERR_NOT_SUPPORTED; a key or value column index out of range, a key dtype the sort
+ * refuses, an aggregate (COUNT included) over Boolean or Utf8, 2^32 rows or more
+ * NQE_ERR_NOT_SUPPORTED.  Zero rows give a 0-row table with every column.  Nothing is kept
+ * between calls.
+ * Out of scope: frames with offsets (n PRECEDING, FOLLOWING); LAG / LEAD / FIRST_VALUE / NTILE;
+ * several different windows in one call (call once per window); SQL parsing. */
+#define NQE_MAX_WINDOW_KEYS 8
+#define NQE_MAX_WINDOW_FUNCS 16
+typedef enum nqe_window_func {
+    NQE_WIN_ROW_NUMBER = 0,
+    NQE_WIN_RANK = 1,
+    NQE_WIN_DENSE_RANK = 2,
+    NQE_WIN_COUNT = 3,
+    NQE_WIN_SUM = 4,
+    NQE_WIN_MIN = 5,
+    NQE_WIN_MAX = 6,
+    NQE_WIN_AVG = 7
+} nqe_window_func;
+typedef enum nqe_window_frame {
+    NQE_FRAME_PARTITION = 0, /* every row of the partition */
+    NQE_FRAME_ROWS = 1,      /* ROWS BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW */
+    NQE_FRAME_RANGE = 2      /* RANGE ... CURRENT ROW: up to the row's LAST peer (SQL's default with ORDER BY) */
+} nqe_window_frame;
+typedef struct nqe_window_spec {
+    int32_t func;   /* nqe_window_func */
+    int32_t column; /* the aggregate's input column; ignored by the three ranking functions */
+    int32_t frame;  /* nqe_window_frame; ignored by the three ranking functions */
+} nqe_window_spec;
+nqe_status nqe_window_execute(nqe_ctx *ctx, const nqe_table *in, const int32_t *partition_cols, int32_t num_partition,
+                              const nqe_sort_key *order_keys, int32_t num_order, const nqe_window_spec *funcs,
+                              int32_t num_funcs, nqe_table **out);
+
 /* ------------------------------------------------------------------ take
  * arrow::compute::take(array, &Int64Array indices, None) over every column
  * (hash_join.rs:239,245): out[j] = in[indices[j]]; `indices` = Int64 column `idx_column` of

@@ -51,7 +51,7 @@ use crate::datasource::{TableRef, TableSource};
 use crate::error::{ErrorCode, Result};
 use crate::logical_plan::expression::{AggregateFunc, Column, ScalarValue};
 use crate::logical_plan::plan::JoinType;
-use crate::logical_plan::schema::NaiveSchema;
+use crate::logical_plan::schema::{NaiveField, NaiveSchema};
 use crate::physical_plan::{
     ColumnExpr, CrossJoin, HashJoin, NestedLoopJoin, PhysicalAggregatePlan, PhysicalBinaryExpr, PhysicalExprRef, PhysicalLimitPlan, PhysicalLiteralExpr, PhysicalOffsetPlan,
     PhysicalPlan, PhysicalPlanRef, PhysicalUnaryExpr, ProjectionPlan, ScanPlan, SelectionPlan,
@@ -72,6 +72,13 @@ pub struct NqeAggregate { pub func: i32, pub column: i32 }
 /// nqe_sort_key: one ORDER BY key (arrow's SortOptions::default() is descending 0, nulls_first 1)
 #[repr(C)] #[derive(Clone, Copy, Debug)]
 pub struct NqeSortKey { pub column: i32, pub descending: i32, pub nulls_first: i32 }
+/// nqe_window_spec: one window function (quirk Q23); `column` and `frame` are ignored by the three ranking functions
+#[repr(C)] #[derive(Clone, Copy, Debug)]
+pub struct NqeWindowSpec { pub func: i32, pub column: i32, pub frame: i32 }
+// nqe_window_func / nqe_window_frame
+pub const NQE_WIN_ROW_NUMBER: i32 = 0; pub const NQE_WIN_RANK: i32 = 1; pub const NQE_WIN_DENSE_RANK: i32 = 2; pub const NQE_WIN_COUNT: i32 = 3;
+pub const NQE_WIN_SUM: i32 = 4; pub const NQE_WIN_MIN: i32 = 5; pub const NQE_WIN_MAX: i32 = 6; pub const NQE_WIN_AVG: i32 = 7;
+pub const NQE_FRAME_PARTITION: i32 = 0; pub const NQE_FRAME_ROWS: i32 = 1; pub const NQE_FRAME_RANGE: i32 = 2;
 pub enum NqeCtx {}
 pub enum NqeTable {}
 pub enum NqeJoinTable {}
@@ -130,6 +137,8 @@ extern "C" {
     fn nqe_cross_join_execute(ctx: *mut NqeCtx, left: *const NqeTable, right: *const NqeTable, out: *mut *mut NqeTable) -> i32;
     fn nqe_nested_loop_join_execute(ctx: *mut NqeCtx, left: *const NqeTable, right: *const NqeTable, left_key: i32, right_key: i32, out: *mut *mut NqeTable) -> i32;
     fn nqe_sort_execute(ctx: *mut NqeCtx, input: *const NqeTable, keys: *const NqeSortKey, num_keys: i32, fetch: i64, out: *mut *mut NqeTable) -> i32;
+    fn nqe_window_execute(ctx: *mut NqeCtx, input: *const NqeTable, partition_cols: *const i32, num_partition: i32, order_keys: *const NqeSortKey, num_order: i32,
+                          funcs: *const NqeWindowSpec, num_funcs: i32, out: *mut *mut NqeTable) -> i32;
 }
 
 // ------------------------------------------------------------------ context, device tables, upload, download
@@ -954,6 +963,58 @@ impl PhysicalPlan for GpuSortPlan {
     fn as_gpu(&self) -> Option<&dyn GpuExec> { Some(self) }
 }
 
+/// Window functions (quirk Q23: the reference has no window expression, logical_plan/expression.rs:22-46): f(...) OVER (PARTITION BY
+/// `partition_by` ORDER BY `order_by`) for every function of `funcs`, all sharing the one window.  The input batches are concatenated and
+/// ONE batch leaves: the input's columns in input order, then one column per function (UInt64 for the ranking functions and count,
+/// Float64 for sum / min / max / avg, no NULLs).  Keys and arguments are column indices; `names` are the new fields' names
+/// (`row_number()`, `sum(x)`, …).  The reference's planner builds no such operator: a front end that plans OVER creates it directly.
+#[derive(Debug)]
+pub struct GpuWindowPlan {
+    input: PhysicalPlanRef, partition_by: Vec<i32>, order_by: Vec<NqeSortKey>, funcs: Vec<NqeWindowSpec>, names: Vec<String>, out_schema: NaiveSchema, ctx: Arc<GpuCtx>,
+}
+impl GpuWindowPlan {
+    pub fn create(ctx: Arc<GpuCtx>, input: PhysicalPlanRef, partition_by: Vec<i32>, order_by: Vec<NqeSortKey>, funcs: Vec<NqeWindowSpec>, names: Vec<String>) -> PhysicalPlanRef {
+        let mut fields: Vec<NaiveField> = input.schema().fields().clone();
+        for (f, name) in funcs.iter().zip(names.iter()) {
+            let dt = if f.func <= NQE_WIN_COUNT { DataType::UInt64 } else { DataType::Float64 };
+            fields.push(NaiveField::new(None, name.as_str(), dt, false));
+        }
+        Arc::new(Self { input, partition_by, order_by, funcs, names, out_schema: NaiveSchema::new(fields), ctx })
+    }
+}
+impl GpuExec for GpuWindowPlan {
+    fn execute_device(&self) -> Result<Vec<GpuBatch>> {
+        let batches = child_device(&self.ctx, &self.input)?;
+        if batches.is_empty() { return Err(ErrorCode::NotSupported("window functions over an empty batch list are not supported on the device path".to_string())); }
+        let all = self.ctx.concat(&batches)?;
+        let mut w = std::ptr::null_mut();
+        self.ctx.check(unsafe { nqe_window_execute(self.ctx.0, all.table.0, self.partition_by.as_ptr(), self.partition_by.len() as i32, self.order_by.as_ptr(),
+                                                   self.order_by.len() as i32, self.funcs.as_ptr(), self.funcs.len() as i32, &mut w) })?;
+        let win = GpuBatch::wrap(w);
+        // the input's columns beside the functions': a view that borrows from both tables, copied into a table of its own
+        // (nqe_table_slice copies) before they go away
+        let mut cols: Vec<NqeColumn> = vec![];
+        for t in [&all.table, &win.table] {
+            for i in 0..t.num_columns() as i32 {
+                let mut info: NqeColumn = unsafe { std::mem::zeroed() };
+                self.ctx.check(unsafe { nqe_table_column(t.0, i, &mut info) })?;
+                cols.push(info);
+            }
+        }
+        let mut both = std::ptr::null_mut();
+        self.ctx.check(unsafe { nqe_table_create(self.ctx.0, cols.as_ptr(), cols.len() as i32, &mut both) })?;
+        let view = GpuBatch::wrap(both);
+        Ok(vec![self.ctx.slice(&view, 0, view.num_rows())?])
+    }
+}
+impl PhysicalPlan for GpuWindowPlan {
+    fn schema(&self) -> &NaiveSchema { &self.out_schema }
+    fn children(&self) -> Result<Vec<PhysicalPlanRef>> { Ok(vec![self.input.clone()]) }
+    fn execute(&self) -> Result<Vec<RecordBatch>> { self.ctx.download_all(&self.execute_device()?, &self.out_schema) }
+    fn as_any(&self) -> &dyn Any { self }
+    fn as_gpu(&self) -> Option<&dyn GpuExec> { Some(self) }
+}
+
 /// PhysicalLimitPlan / PhysicalOffsetPlan (limit.rs:32-49, offset.rs:30-51) over device batches: whole batches are passed on,
 /// a cut batch is nqe_table_slice — so a LIMIT above a device operator downloads `n` rows, not the operator's whole result
 #[derive(Debug)]
@@ -1067,6 +1128,9 @@ pub fn rewrite_sharded(ctx: &Arc<GpuCtx>, comm: Option<&Arc<GpuComm>>, plan: Phy
             return Ok(GpuSortPlan::create(ctx.clone(), rewrite(ctx, s.input.clone())?, s.keys.clone(), Some(fetch)));
         }
         return Ok(GpuLimitPlan::create_limit(ctx.clone(), rewrite(ctx, l.input.clone())?, l.n));
+    }
+    if let Some(w) = any.downcast_ref::<GpuWindowPlan>() { // keeps its operator, with a rewritten child (a limit above it stays a limit)
+        return Ok(GpuWindowPlan::create(ctx.clone(), rewrite(ctx, w.input.clone())?, w.partition_by.clone(), w.order_by.clone(), w.funcs.clone(), w.names.clone()));
     }
     if let Some(o) = any.downcast_ref::<PhysicalOffsetPlan>() {
         return Ok(GpuLimitPlan::create_offset(ctx.clone(), rewrite(ctx, o.input.clone())?, o.n));

@@ -75,6 +75,27 @@ class AggregateFunc(enum.IntEnum):
     Avg = 4
 
 
+class WindowFunc(enum.IntEnum):
+    """nqe_window_func (include/nqe.h; quirk Q23: the reference has no window expression)"""
+
+    RowNumber = 0
+    Rank = 1
+    DenseRank = 2
+    Count = 3
+    Sum = 4
+    Min = 5
+    Max = 6
+    Avg = 7
+
+
+class WindowFrame(enum.IntEnum):
+    """nqe_window_frame: every row of the partition; ROWS / RANGE BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW"""
+
+    Partition = 0
+    Rows = 1
+    Range = 2
+
+
 class Status(enum.IntEnum):
     """nqe_status; 1..13 mirror enum ErrorCode (src/error.rs:13-40)."""
 

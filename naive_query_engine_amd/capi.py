@@ -29,7 +29,7 @@ SYMBOLS = [
     "nqe_filter", "nqe_selection_execute", "nqe_projection_execute", "nqe_selection_projection_execute",
     "nqe_aggregate_execute", "nqe_aggregate_partial", "nqe_aggregate_merge", "nqe_aggregate_merge_packed", "nqe_group_aggregate_execute", "nqe_hash_join_execute",
     "nqe_hash_join_build", "nqe_hash_join_probe", "nqe_join_table_release", "nqe_join_marks_create", "nqe_join_marks_release",
-    "nqe_hash_join_probe_outer", "nqe_hash_join_unmatched_build", "nqe_hash_join_build_keys", "nqe_hash_join_probe_keys", "nqe_hash_join_execute_keys", "nqe_hash_join_probe_semi", "nqe_hash_join_marked_build", "nqe_cross_join_execute", "nqe_nested_loop_join_execute", "nqe_sort_execute", "nqe_take", "nqe_synth_fill",
+    "nqe_hash_join_probe_outer", "nqe_hash_join_unmatched_build", "nqe_hash_join_build_keys", "nqe_hash_join_probe_keys", "nqe_hash_join_execute_keys", "nqe_hash_join_probe_semi", "nqe_hash_join_marked_build", "nqe_cross_join_execute", "nqe_nested_loop_join_execute", "nqe_sort_execute", "nqe_window_execute", "nqe_take", "nqe_synth_fill",
     "nqe_device_alloc", "nqe_device_free",
     "nqe_comm_get_unique_id", "nqe_comm_rccl_version", "nqe_comm_create", "nqe_comm_create_custom", "nqe_comm_create_p2p", "nqe_comm_destroy", "nqe_comm_rank",
     "nqe_comm_world", "nqe_table_all_gather", "nqe_sharded_aggregate_execute", "nqe_sharded_hash_join_probe",
@@ -61,6 +61,11 @@ class ArrowArrayStruct(C.Structure):
 class NqeSortKey(C.Structure):
     """nqe_sort_key (include/nqe.h): one ORDER BY key; arrow-rs' SortOptions::default() is descending 0, nulls_first 1"""
     _fields_ = [("column", C.c_int32), ("descending", C.c_int32), ("nulls_first", C.c_int32)]
+
+
+class NqeWindowSpec(C.Structure):
+    """nqe_window_spec (include/nqe.h): one window function; `column` and `frame` are ignored by the three ranking functions"""
+    _fields_ = [("func", C.c_int32), ("column", C.c_int32), ("frame", C.c_int32)]
 
 
 _P2P_SEND_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p)
@@ -149,6 +154,7 @@ def lib():
         "nqe_cross_join_execute": (i32, [vp, vp, vp, pvp]),
         "nqe_nested_loop_join_execute": (i32, [vp, vp, vp, i32, i32, pvp]),
         "nqe_sort_execute": (i32, [vp, vp, C.POINTER(NqeSortKey), i32, i64, pvp]),
+        "nqe_window_execute": (i32, [vp, vp, C.POINTER(i32), i32, C.POINTER(NqeSortKey), i32, C.POINTER(NqeWindowSpec), i32, pvp]),
         "nqe_take": (i32, [vp, vp, vp, i32, pvp]),
         "nqe_synth_fill": (i32, [vp, i32, u64, i64, i64, u64, i64, vp]),
         "nqe_device_alloc": (i32, [vp, C.c_size_t, pvp]),
@@ -502,6 +508,22 @@ class Context:
         arr = (NqeSortKey * max(1, len(ks)))(*[NqeSortKey(int(c), int(bool(d)), int(bool(nf))) for c, d, nf in ks])
         h = C.c_void_p()
         self.check(lib().nqe_sort_execute(self.handle, table.handle, arr, len(ks), -1 if fetch is None else int(fetch), C.byref(h)))
+        return Table(self, h)
+
+    def window(self, table: "Table", partition_by, order_by, funcs) -> "Table":
+        """window functions over one table (quirk Q23): `partition_by` column indices, `order_by` keys as order_by() takes them, `funcs`
+        a list of (WindowFunc, column or None, WindowFrame or None) — column and frame are ignored by the ranking functions, a missing
+        frame is WindowFrame.Range (SQL's default with ORDER BY).  ONE table of len(funcs) columns in INPUT row order; put it beside the input with
+        append_columns"""
+        parts = [int(c) for c in partition_by]
+        ks = [(k, False, True) if isinstance(k, int) else tuple(k) + (False, True)[len(k) - 1:] for k in order_by]
+        fs = [(f,) if isinstance(f, int) else tuple(f) for f in funcs]
+        fs = [(f + (None, None))[:3] for f in fs]
+        parr = (C.c_int32 * max(1, len(parts)))(*parts)
+        karr = (NqeSortKey * max(1, len(ks)))(*[NqeSortKey(int(c), int(bool(d)), int(bool(nf))) for c, d, nf in ks])
+        farr = (NqeWindowSpec * max(1, len(fs)))(*[NqeWindowSpec(int(f), 0 if c is None else int(c), 2 if fr is None else int(fr)) for f, c, fr in fs])
+        h = C.c_void_p()
+        self.check(lib().nqe_window_execute(self.handle, table.handle, parr, len(parts), karr, len(ks), farr, len(fs), C.byref(h)))
         return Table(self, h)
 
     def append_columns(self, table: "Table", extras: Sequence["Table"]) -> "Table":

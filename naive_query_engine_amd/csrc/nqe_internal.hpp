@@ -264,6 +264,16 @@ void pack_bytes_to_bits(nqe_ctx *ctx, const uint8_t *bytes, int64_t n, uint64_t 
 void radix_sort_pairs_u64(nqe_ctx *ctx, const uint64_t *keys_in, const uint32_t *vals_in, uint64_t *keys_out,
                           uint32_t *vals_out, int64_t n, bool signed_order);
 
+// ---- the ORDER BY permutation (order_by.hip), shared with the window operator (window.hip)
+// the buffers of one permutation build; `cur` is the u32 permutation (output position -> input row), null while it is the identity
+struct SortPermutation {
+    BufRef keys_in, keys_out, iota, perm[2], order;
+    const uint32_t *cur = nullptr;
+};
+// The stable multi-key permutation of nqe_sort_execute: keys[0] most significant, built least significant key first.  The caller has
+// checked the keys (column indices, dtypes) and that 1 < in->rows < 2^32.  Returns hold->cur; `hold` keeps the buffers alive.
+const uint32_t *build_sort_permutation(nqe_ctx *ctx, const nqe_table *in, const nqe_sort_key *keys, int32_t num_keys, SortPermutation *hold);
+
 // ---- Utf8 keys (strings.hip): exact string → representative-row encoding
 struct Utf8Dict {
     BufRef slots;      // int64 representative build row per slot, -1 = empty

@@ -122,39 +122,85 @@ void ob_launch_encode(nqe_ctx *ctx, int kind, const ObArgs &a) {
     }
 }
 
-// the permutation being built: `cur` is null while it is still the identity
+// the permutation being built (SortPermutation: `cur` is null while it is still the identity)
 struct ObState {
     nqe_ctx *ctx;
     int64_t n;
-    BufRef keys_in, keys_out, iota, perm[2], order;
-    const uint32_t *cur = nullptr;
+    SortPermutation &p;
     int next = 0;
 
     // one stable pass: rows that tie on the encoded word keep the order they have in `cur`
     void pass(int kind, ObArgs a) {
         a.n = n;
-        a.perm = cur;
-        a.keys = static_cast<uint64_t *>(keys_in->ptr);
-        a.iota = cur ? nullptr : static_cast<uint32_t *>(iota->ptr);
+        a.perm = p.cur;
+        a.keys = static_cast<uint64_t *>(p.keys_in->ptr);
+        a.iota = p.cur ? nullptr : static_cast<uint32_t *>(p.iota->ptr);
         ob_launch_encode(ctx, kind, a);
-        uint32_t *dst = static_cast<uint32_t *>(perm[next]->ptr);
-        uint64_t *ko = static_cast<uint64_t *>(keys_out->ptr);
-        const uint32_t *io = static_cast<const uint32_t *>(iota->ptr);
-        if (!cur) {
+        uint32_t *dst = static_cast<uint32_t *>(p.perm[next]->ptr);
+        uint64_t *ko = static_cast<uint64_t *>(p.keys_out->ptr);
+        const uint32_t *io = static_cast<const uint32_t *>(p.iota->ptr);
+        if (!p.cur) {
             radix_sort_pairs_u64(ctx, a.keys, io, ko, dst, n, false);
         } else if (n > OB_SMALL) {
-            radix_sort_pairs_u64(ctx, a.keys, cur, ko, dst, n, false);
+            radix_sort_pairs_u64(ctx, a.keys, p.cur, ko, dst, n, false);
         } else {
-            uint32_t *ord = static_cast<uint32_t *>(order->ptr);
+            uint32_t *ord = static_cast<uint32_t *>(p.order->ptr);
             radix_sort_pairs_u64(ctx, a.keys, io, ko, ord, n, false);
-            launch(ctx, "ob_compose", ob_compose_kernel, dim3(unsigned(stream_grid(ctx, n, OB_THREADS))), dim3(OB_THREADS), 0, cur, (const uint32_t *)ord, n, dst);
+            launch(ctx, "ob_compose", ob_compose_kernel, dim3(unsigned(stream_grid(ctx, n, OB_THREADS))), dim3(OB_THREADS), 0, p.cur, (const uint32_t *)ord, n, dst);
         }
-        cur = dst;
+        p.cur = dst;
         next ^= 1;
     }
 };
 
 } // namespace
+
+// the stable permutation of `in`'s rows by `keys` (checked by the caller; in->rows in (1, 2^32)), least significant key first
+const uint32_t *build_sort_permutation(nqe_ctx *ctx, const nqe_table *in, const nqe_sort_key *keys, int32_t num_keys, SortPermutation *hold) {
+    const int64_t n = in->rows;
+    ObState st{ctx, n, *hold};
+    SortPermutation &p = *hold;
+    p.keys_in = dev_alloc(ctx, size_t(n) * 8);
+    p.keys_out = dev_alloc(ctx, size_t(n) * 8);
+    p.iota = dev_alloc(ctx, size_t(n) * 4);
+    p.perm[0] = dev_alloc(ctx, size_t(n) * 4);
+    if (n <= OB_SMALL) p.order = dev_alloc(ctx, size_t(n) * 4);
+    for (int32_t k = num_keys - 1; k >= 0; --k) {
+        const DevColumn &c = in->cols[size_t(keys[k].column)];
+        ObArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.valid = c.null_count == 0 ? nullptr : c.valid();
+        a.complement = keys[k].descending ? ~uint64_t(0) : 0;
+        auto pass = [&](int kind) {
+            if (!p.perm[1] && p.cur) p.perm[1] = dev_alloc(ctx, size_t(n) * 4); // (a single pass needs one buffer)
+            st.pass(kind, a);
+        };
+        if (c.dtype == NQE_UTF8) {
+            a.off = static_cast<const int32_t *>(c.values->ptr);
+            a.data = c.data ? static_cast<const uint8_t *>(c.data->ptr) : nullptr;
+            BufRef d = dev_alloc_zero(ctx, 8);
+            launch(ctx, "ob_max_len", ob_max_len_kernel, dim3(unsigned(stream_grid(ctx, n, OB_THREADS, 4))), dim3(OB_THREADS), 0, a.off, a.valid, n, static_cast<uint32_t *>(d->ptr));
+            const int64_t max_len = int64_t(read_scalar(ctx, static_cast<const uint32_t *>(d->ptr)));
+            pass(OB_UTF8_LEN);
+            for (int64_t ch = (max_len + 7) / 8 - 1; ch >= 0; --ch) {
+                a.chunk = ch;
+                pass(OB_UTF8_CHUNK);
+            }
+        } else if (c.dtype == NQE_BOOLEAN) {
+            a.bits = c.bits();
+            pass(OB_BOOL);
+        } else {
+            a.words = c.words();
+            pass(c.dtype == NQE_INT64 ? OB_I64 : c.dtype == NQE_UINT64 ? OB_U64 : OB_F64);
+        }
+        if (a.valid) { // the flag alone: a full-range Int64 leaves no spare bit for it
+            a.null_word = keys[k].nulls_first ? 0 : 1;
+            a.complement = 0;
+            pass(OB_NULL_FLAG);
+        }
+    }
+    return p.cur;
+}
 
 } // namespace nqe
 
@@ -174,50 +220,8 @@ nqe_status nqe_sort_execute(nqe_ctx *ctx, const nqe_table *in, const nqe_sort_ke
     if (n >= (int64_t(1) << 32)) fail(NQE_ERR_NOT_SUPPORTED, "order by: " + std::to_string(n) + " rows, the sort handles fewer than 2^32");
     const int64_t m = fetch < 0 ? n : std::min(fetch, n);
 
-    ObState st;
-    st.ctx = ctx;
-    st.n = n;
-    if (n > 1 && m > 0) {
-        st.keys_in = dev_alloc(ctx, size_t(n) * 8);
-        st.keys_out = dev_alloc(ctx, size_t(n) * 8);
-        st.iota = dev_alloc(ctx, size_t(n) * 4);
-        st.perm[0] = dev_alloc(ctx, size_t(n) * 4);
-        if (n <= OB_SMALL) st.order = dev_alloc(ctx, size_t(n) * 4);
-        for (int32_t k = num_keys - 1; k >= 0; --k) {
-            const DevColumn &c = in->cols[size_t(keys[k].column)];
-            ObArgs a;
-            std::memset(&a, 0, sizeof(a));
-            a.valid = c.null_count == 0 ? nullptr : c.valid();
-            a.complement = keys[k].descending ? ~uint64_t(0) : 0;
-            auto pass = [&](int kind) {
-                if (!st.perm[1] && st.cur) st.perm[1] = dev_alloc(ctx, size_t(n) * 4); // (a single pass needs one buffer)
-                st.pass(kind, a);
-            };
-            if (c.dtype == NQE_UTF8) {
-                a.off = static_cast<const int32_t *>(c.values->ptr);
-                a.data = c.data ? static_cast<const uint8_t *>(c.data->ptr) : nullptr;
-                BufRef d = dev_alloc_zero(ctx, 8);
-                launch(ctx, "ob_max_len", ob_max_len_kernel, dim3(unsigned(stream_grid(ctx, n, OB_THREADS, 4))), dim3(OB_THREADS), 0, a.off, a.valid, n, static_cast<uint32_t *>(d->ptr));
-                const int64_t max_len = int64_t(read_scalar(ctx, static_cast<const uint32_t *>(d->ptr)));
-                pass(OB_UTF8_LEN);
-                for (int64_t ch = (max_len + 7) / 8 - 1; ch >= 0; --ch) {
-                    a.chunk = ch;
-                    pass(OB_UTF8_CHUNK);
-                }
-            } else if (c.dtype == NQE_BOOLEAN) {
-                a.bits = c.bits();
-                pass(OB_BOOL);
-            } else {
-                a.words = c.words();
-                pass(c.dtype == NQE_INT64 ? OB_I64 : c.dtype == NQE_UINT64 ? OB_U64 : OB_F64);
-            }
-            if (a.valid) { // the flag alone: a full-range Int64 leaves no spare bit for it
-                a.null_word = keys[k].nulls_first ? 0 : 1;
-                a.complement = 0;
-                pass(OB_NULL_FLAG);
-            }
-        }
-    }
+    SortPermutation st;
+    if (n > 1 && m > 0) build_sort_permutation(ctx, in, keys, num_keys, &st);
 
     // the first m positions as take's int64 row list; the launch's label carries m (what a test of `fetch` asks nqe_ctx_timing_query for)
     BufRef pos = dev_alloc(ctx, size_t(m) * 8 + 8);

@@ -200,12 +200,24 @@ class RecordBatch {
                                               a.validity.empty() ? nullptr : a.validity.data(), nullptr));
         return a;
     }
-    RecordBatch with_table(NaiveSchema schema, nqe_table *t) const { return RecordBatch(ctx_, std::move(schema), t); }
+    RecordBatch with_table(NaiveSchema schema, nqe_table *t) const {
+        RecordBatch r(ctx_, std::move(schema), t);
+        r.keep_ = keep_;
+        return r;
+    }
+    // `t` borrows columns of `parents` (nqe_table_create over nqe_table_column): they live as long as the batch and whatever with_table derives from it
+    RecordBatch with_view(NaiveSchema schema, nqe_table *t, const std::vector<std::shared_ptr<nqe_table>> &parents) const {
+        RecordBatch r = with_table(std::move(schema), t);
+        r.keep_.insert(r.keep_.end(), parents.begin(), parents.end());
+        return r;
+    }
+    const std::shared_ptr<nqe_table> &shared() const { return table_; }
 
   private:
     ContextRef ctx_;
     NaiveSchema schema_;
     std::shared_ptr<nqe_table> table_;
+    std::vector<std::shared_ptr<nqe_table>> keep_; // the tables a view borrows from
 };
 
 // ---------------------------------------------------------------- physical_plan/expression/*.rs
@@ -1083,6 +1095,108 @@ struct PhysicalSortPlan : PhysicalPlan {
     }
 };
 
+// ---------------------------------------------------------------- window functions (no reference file: logical_plan/expression.rs:22-46 has no window expression)
+// Quirk Q23: f(...) OVER (PARTITION BY partition_by ORDER BY order_by) for every function of `funcs`; all of them share the one window.
+// Like PhysicalSortPlan the input batches are concatenated and ONE batch leaves: the input's columns in input order, then one column per
+// function (row_number(), rank(), dense_rank(), count(x), sum(x), …).  A key or argument that is a bare ColumnExpr is passed by index;
+// any other expression is evaluated into a temporary column that never reaches the output.
+struct WindowFunction {
+    nqe_window_func func;
+    PhysicalExprRef expr; // null for the three ranking functions
+    nqe_window_frame frame;
+    WindowFunction(nqe_window_func f, PhysicalExprRef e = nullptr, nqe_window_frame fr = NQE_FRAME_RANGE) : func(f), expr(std::move(e)), frame(fr) {
+        if (!is_ranking() && !expr) throw ErrorCode(ErrorCode::PlanError, std::string("window function ") + label() + " needs an argument");
+    }
+    bool is_ranking() const { return func == NQE_WIN_ROW_NUMBER || func == NQE_WIN_RANK || func == NQE_WIN_DENSE_RANK; }
+    const char *label() const {
+        static const char *const names[] = {"row_number", "rank", "dense_rank", "count", "sum", "min", "max", "avg"};
+        return names[int(func)];
+    }
+    NaiveField data_field(const NaiveSchema &schema) const {
+        if (is_ranking()) return NaiveField(std::nullopt, std::string(label()) + "()", DataType::UInt64, false);
+        const ColumnExpr *c = expr->as_column();
+        const std::string arg = c ? schema.field(c->resolve(schema)).name() : std::string("expr");
+        return NaiveField(std::nullopt, std::string(label()) + "(" + arg + ")", func == NQE_WIN_COUNT ? DataType::UInt64 : DataType::Float64, false);
+    }
+};
+struct PhysicalWindowPlan : PhysicalPlan {
+    PhysicalPlanRef input;
+    std::vector<PhysicalExprRef> partition_by;
+    std::vector<PhysicalSortExpr> order_by;
+    std::vector<WindowFunction> funcs;
+    NaiveSchema schema_;
+    static PhysicalPlanRef create(PhysicalPlanRef input, std::vector<PhysicalExprRef> partition_by, std::vector<PhysicalSortExpr> order_by, std::vector<WindowFunction> funcs) {
+        auto p = std::make_shared<PhysicalWindowPlan>();
+        p->input = std::move(input); p->partition_by = std::move(partition_by); p->order_by = std::move(order_by); p->funcs = std::move(funcs);
+        p->schema_ = p->output_schema(p->input->schema());
+        return p;
+    }
+    NaiveSchema output_schema(const NaiveSchema &below) const {
+        std::vector<NaiveField> fields = below.fields();
+        for (auto &f : funcs) fields.push_back(f.data_field(below));
+        return NaiveSchema(fields);
+    }
+    const NaiveSchema &schema() const override { return schema_; }
+    std::vector<PhysicalPlanRef> children() const override { return {input}; }
+    std::vector<RecordBatch> execute() override {
+        std::vector<RecordBatch> batches = input->execute();
+        if (batches.empty()) throw ErrorCode(ErrorCode::NotSupported, "window functions over an empty batch list are not supported on the device path");
+        const ContextRef &ctx = batches[0].ctx();
+        const NaiveSchema &s = batches[0].schema();
+        auto release = [](nqe_table *p) { nqe_table_release(p); };
+        std::vector<std::shared_ptr<nqe_table>> guards;
+        std::shared_ptr<nqe_table> in = batches[0].shared();
+        if (batches.size() > 1) {
+            std::vector<const nqe_table *> parts;
+            for (auto &b : batches) parts.push_back(b.raw());
+            nqe_table *c = nullptr;
+            ctx->check(nqe_table_concat(ctx->raw(), parts.data(), int32_t(parts.size()), &c));
+            in = std::shared_ptr<nqe_table>(c, release);
+        }
+        const int32_t ncols = nqe_table_num_columns(in.get());
+        std::vector<nqe_column> cols(static_cast<size_t>(ncols)); // `in`'s columns, borrowed; the temporaries follow
+        for (int32_t i = 0; i < ncols; ++i) ctx->check(nqe_table_column(in.get(), i, &cols[size_t(i)]));
+        auto column_of = [&](const PhysicalExprRef &e) {
+            if (const ColumnExpr *c = e->as_column()) return int32_t(c->resolve(s));
+            std::vector<nqe_expr_node> nodes;
+            e->flatten(s, nodes);
+            nqe_table *t = nullptr;
+            ctx->check(nqe_expr_evaluate(ctx->raw(), in.get(), nodes.data(), int32_t(nodes.size()), &t));
+            guards.emplace_back(t, release);
+            nqe_column tc;
+            ctx->check(nqe_table_column(t, 0, &tc));
+            cols.push_back(tc);
+            return int32_t(cols.size()) - 1;
+        };
+        std::vector<int32_t> parts;
+        std::vector<nqe_sort_key> keys;
+        std::vector<nqe_window_spec> specs;
+        for (auto &e : partition_by) parts.push_back(column_of(e));
+        for (auto &e : order_by) keys.push_back(nqe_sort_key{column_of(e.expr), e.descending ? 1 : 0, e.nulls_first ? 1 : 0});
+        for (auto &f : funcs) specs.push_back(nqe_window_spec{int32_t(f.func), f.expr ? column_of(f.expr) : 0, int32_t(f.frame)});
+        const nqe_table *source = in.get();
+        if (cols.size() > size_t(ncols)) {
+            nqe_table *wide = nullptr;
+            ctx->check(nqe_table_create(ctx->raw(), cols.data(), int32_t(cols.size()), &wide));
+            guards.emplace_back(wide, release);
+            source = wide;
+        }
+        nqe_table *w = nullptr;
+        ctx->check(nqe_window_execute(ctx->raw(), source, parts.data(), int32_t(parts.size()), keys.data(), int32_t(keys.size()), specs.data(), int32_t(specs.size()), &w));
+        std::shared_ptr<nqe_table> win(w, release);
+        // the input's columns beside the functions': a view over both tables, which the batch keeps alive
+        cols.resize(size_t(ncols));
+        for (int32_t i = 0; i < int32_t(funcs.size()); ++i) {
+            nqe_column c;
+            ctx->check(nqe_table_column(win.get(), i, &c));
+            cols.push_back(c);
+        }
+        nqe_table *both = nullptr;
+        ctx->check(nqe_table_create(ctx->raw(), cols.data(), int32_t(cols.size()), &both));
+        return {batches[0].with_view(output_schema(s), both, {in, win})};
+    }
+};
+
 // ---------------------------------------------------------------- physical_plan/visitor.rs:4-24
 struct PhysicalPlanVisitor { // trait PhysicalPlanVistor
     virtual ~PhysicalPlanVisitor() = default;
@@ -1217,6 +1331,7 @@ inline PhysicalPlanRef rewrite(const PhysicalPlanRef &plan) {
         return PhysicalLimitPlan::create(rewrite(l->input), l->n);
     }
     if (auto srt = std::dynamic_pointer_cast<PhysicalSortPlan>(plan)) return PhysicalSortPlan::create(rewrite(srt->input), srt->sort_exprs, srt->fetch);
+    if (auto w = std::dynamic_pointer_cast<PhysicalWindowPlan>(plan)) return PhysicalWindowPlan::create(rewrite(w->input), w->partition_by, w->order_by, w->funcs);
     if (auto o = std::dynamic_pointer_cast<PhysicalOffsetPlan>(plan)) return PhysicalOffsetPlan::create(rewrite(o->input), o->n);
     if (auto o = std::dynamic_pointer_cast<HashOuterJoin>(plan)) return HashOuterJoin::create(rewrite(o->left), rewrite(o->right), o->on, o->join_type, o->schema_);
     if (auto m = std::dynamic_pointer_cast<MultiKeyHashJoin>(plan)) return MultiKeyHashJoin::create(rewrite(m->left), rewrite(m->right), m->on, m->join_type, m->schema_);

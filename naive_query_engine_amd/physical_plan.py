@@ -21,7 +21,7 @@ from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple
 
 from . import capi
-from .arrow_host import AggregateFunc, Column, DType, ErrorCode, Field, RecordBatch, Status
+from .arrow_host import AggregateFunc, Column, DType, ErrorCode, Field, RecordBatch, Status, WindowFrame, WindowFunc
 from .expression import ColumnExpr, PhysicalExpr
 
 NaiveSchema = List[Field]  # src/logical_plan/schema.rs (qualifiers are ignored at physical planning, Q12)
@@ -801,3 +801,76 @@ class PhysicalSortPlan(PhysicalPlan):
             return [DeviceRecordBatch(fields, ctx.order_by(table, keys, self.fetch))]
         out = ctx.order_by(ctx.append_columns(table, temps), keys, self.fetch)
         return [DeviceRecordBatch(fields, ctx.project(out, list(range(len(fields)))))]
+
+
+# ----------------------------------------------------------------------------- window functions
+_WINDOW_LABELS = {WindowFunc.RowNumber: "row_number", WindowFunc.Rank: "rank", WindowFunc.DenseRank: "dense_rank", WindowFunc.Count: "count",
+                  WindowFunc.Sum: "sum", WindowFunc.Min: "min", WindowFunc.Max: "max", WindowFunc.Avg: "avg"}
+_WINDOW_RANKING = (WindowFunc.RowNumber, WindowFunc.Rank, WindowFunc.DenseRank)
+
+
+class WindowFunction:
+    """one function of a window: ROW_NUMBER / RANK / DENSE_RANK (no argument, no frame) or one of Q10's count / sum / min / max / avg
+    over `expr` and the rows of `frame` (default: RANGE ... CURRENT ROW, SQL's default with ORDER BY)"""
+
+    def __init__(self, func: WindowFunc, expr: Optional[PhysicalExpr] = None, frame: WindowFrame = WindowFrame.Range):
+        self.func, self.expr, self.frame = WindowFunc(func), expr, WindowFrame(frame)
+        if self.func not in _WINDOW_RANKING and expr is None:
+            raise ErrorCode(Status.PlanError, f"window function {_WINDOW_LABELS[self.func]} needs an argument")
+
+    @staticmethod
+    def create(func: WindowFunc, expr: Optional[PhysicalExpr] = None, frame: WindowFrame = WindowFrame.Range) -> "WindowFunction":
+        return WindowFunction(func, expr, frame)
+
+    def data_field(self, schema: NaiveSchema) -> Field:
+        label = _WINDOW_LABELS[self.func]
+        if self.func in _WINDOW_RANKING:
+            return Field(f"{label}()", DType.UINT64, False)
+        arg = schema[self.expr.resolve(schema)].name if isinstance(self.expr, ColumnExpr) else repr(self.expr)
+        return Field(f"{label}({arg})", DType.UINT64 if self.func == WindowFunc.Count else DType.FLOAT64, False)
+
+    def __repr__(self):
+        return f"WindowFunction({self.func.name}, {self.expr!r}, {self.frame.name})"
+
+
+class PhysicalWindowPlan(PhysicalPlan):
+    """f(...) OVER (PARTITION BY partition_by ORDER BY order_by) for every function of `funcs` (quirk Q23; the reference has no window
+    expression, logical_plan/expression.rs:22-46): all functions share the one window.  Like PhysicalSortPlan the input batches are
+    concatenated and ONE batch leaves: the input's columns in input order, then one column per function.  A key or argument that is a
+    bare ColumnExpr is passed by index; any other expression is evaluated into a temporary column that never reaches the output."""
+
+    def __init__(self, input: PhysicalPlan, partition_by: Sequence[PhysicalExpr], order_by: Sequence[PhysicalSortExpr], funcs: Sequence[WindowFunction]):
+        self.input, self.partition_by, self.order_by, self.funcs = input, list(partition_by), list(order_by), list(funcs)
+
+    @staticmethod
+    def create(input: PhysicalPlan, partition_by: Sequence[PhysicalExpr], order_by: Sequence[PhysicalSortExpr], funcs: Sequence[WindowFunction]) -> "PhysicalWindowPlan":
+        return PhysicalWindowPlan(input, partition_by, order_by, funcs)
+
+    def schema(self):
+        s = list(self.input.schema())
+        return s + [f.data_field(s) for f in self.funcs]
+
+    def children(self):
+        return [self.input]
+
+    def execute(self):
+        batches = self.input.execute()
+        if not batches:
+            raise ErrorCode(Status.NotSupported, "window functions over an empty batch list are not supported on the device path")
+        ctx = _ctx_of(batches)
+        fields = batches[0].fields
+        table = batches[0].table if len(batches) == 1 else ctx.concat([b.table for b in batches])
+        temps = []
+
+        def column_of(expr):
+            if isinstance(expr, ColumnExpr):
+                return expr.resolve(fields)
+            temps.append(ctx.expr_evaluate(table, expr.flatten(fields)))
+            return len(fields) + len(temps) - 1
+
+        parts = [column_of(e) for e in self.partition_by]
+        keys = [(column_of(e.expr), e.descending, e.nulls_first) for e in self.order_by]
+        specs = [(f.func, None if f.expr is None else column_of(f.expr), f.frame) for f in self.funcs]
+        out = ctx.window(ctx.append_columns(table, temps) if temps else table, parts, keys, specs)
+        out_fields = list(fields) + [f.data_field(fields) for f in self.funcs]
+        return [DeviceRecordBatch(out_fields, ctx.append_columns(table, [ctx.project(out, [i]) for i in range(len(self.funcs))]))]

@@ -1,0 +1,179 @@
+// The host analysis of the window operator (naive_query_engine_amd/csrc/window_plan.hpp) on the CPU: every refusal in the order
+// include/nqe.h states, the distinct value columns with their scan operators, the position arrays a function list reads, and the tile
+// and carry counts.  Includes that header alone.
+//   g++ -std=c++17 -I naive_query_engine_amd/csrc tests/cpp/test_window_plan.cpp && ./a.out
+#include <cstdio>
+#include <string>
+
+#include "window_plan.hpp"
+
+using namespace nqe;
+
+static int failures = 0;
+#define CHECK(cond)                                                              \
+    do {                                                                         \
+        if (!(cond)) {                                                           \
+            if (++failures <= 40) std::printf("%s:%d: CHECK(%s)\n", __FILE__, __LINE__, #cond); \
+        }                                                                        \
+    } while (0)
+
+enum { I, U, F, B, S, NONE, NCOLS };
+static const int kDtypes[NCOLS] = {NQE_INT64, NQE_UINT64, NQE_FLOAT64, NQE_BOOLEAN, NQE_UTF8, NQE_NULLTYPE};
+using Keys = std::vector<nqe_sort_key>;
+using Funcs = std::vector<nqe_window_spec>;
+
+struct Call {
+    bool ctx = true, in = true, out = true;
+    std::vector<int32_t> parts;
+    Keys order;
+    Funcs funcs{{NQE_WIN_RANK, 0, 0}};
+    int64_t rows = 100;
+    bool null_parts = false, null_order = false, null_funcs = false;
+    int32_t num_parts = -1, num_order = -1, num_funcs = -1; // -1: the vector's size
+};
+
+// the status plan_window ends in (NQE_OK: it returned), and its message
+static int status(const Call &c, std::string *msg = nullptr, WindowPlan *plan = nullptr) {
+    try {
+        WindowPlan p = plan_window(c.ctx, c.in, c.out, kDtypes, NCOLS, c.rows, c.null_parts ? nullptr : c.parts.data(), c.num_parts < 0 ? int32_t(c.parts.size()) : c.num_parts,
+                                   c.null_order ? nullptr : c.order.data(), c.num_order < 0 ? int32_t(c.order.size()) : c.num_order, c.null_funcs ? nullptr : c.funcs.data(),
+                                   c.num_funcs < 0 ? int32_t(c.funcs.size()) : c.num_funcs);
+        if (plan) *plan = p;
+        return NQE_OK;
+    } catch (const Error &e) {
+        if (msg) *msg = e.msg;
+        return e.code;
+    }
+}
+
+static void test_errors_in_order() {
+    Call ok;
+    CHECK(status(ok) == NQE_OK);
+    // 1. NULL ctx / in / out, a NULL array with a positive count
+    for (int k = 0; k < 3; ++k) {
+        Call c;
+        (k == 0 ? c.ctx : k == 1 ? c.in : c.out) = false;
+        c.funcs = {{99, 0, 0}}; // … before anything else
+        CHECK(status(c) == NQE_ERR_INVALID_ARGUMENT);
+    }
+    {
+        Call c; c.null_parts = true; c.num_parts = 1; CHECK(status(c) == NQE_ERR_INVALID_ARGUMENT);
+        Call d; d.null_order = true; d.num_order = 2; CHECK(status(d) == NQE_ERR_INVALID_ARGUMENT);
+        Call e; e.null_funcs = true; e.num_funcs = 1; CHECK(status(e) == NQE_ERR_INVALID_ARGUMENT);
+        Call f; f.null_parts = f.null_order = true; f.num_parts = f.num_order = 0; CHECK(status(f) == NQE_OK); // a NULL array with count 0 is fine
+    }
+    // 2. func or frame outside its enum — before the empty list, the limits, the indices
+    std::string msg;
+    for (int bad : {-1, 8, 1000}) {
+        Call c; c.funcs = Funcs(20, nqe_window_spec{NQE_WIN_RANK, 0, 0}); c.funcs[19].func = bad; c.parts = {99};
+        CHECK(status(c, &msg) == NQE_ERR_INVALID_ARGUMENT && msg == "window: unknown window function");
+    }
+    for (int bad : {-1, 3}) {
+        Call c; c.funcs = {{NQE_WIN_SUM, 99, bad}};
+        CHECK(status(c, &msg) == NQE_ERR_INVALID_ARGUMENT && msg == "window: unknown frame");
+        Call r; r.funcs = {{NQE_WIN_DENSE_RANK, 99, bad}}; // column and frame are ignored by the ranking functions
+        CHECK(status(r) == NQE_OK);
+    }
+    // 3. no functions
+    {
+        Call c; c.funcs.clear(); c.parts = std::vector<int32_t>(9, 99);
+        CHECK(status(c, &msg) == NQE_ERR_PLAN && msg == "window: the list of window functions is empty");
+        Call d; d.num_funcs = 0; // an array with count 0
+        CHECK(status(d) == NQE_ERR_PLAN);
+    }
+    // 4. the limits — before the indices
+    {
+        Call c; c.parts = std::vector<int32_t>(NQE_MAX_WINDOW_KEYS + 1, 99);
+        CHECK(status(c, &msg) == NQE_ERR_NOT_SUPPORTED && msg.find("at most 8 partition keys") != std::string::npos);
+        Call d; d.order = Keys(NQE_MAX_WINDOW_KEYS + 1, nqe_sort_key{99, 0, 1});
+        CHECK(status(d, &msg) == NQE_ERR_NOT_SUPPORTED && msg.find("at most 8 partition keys") != std::string::npos);
+        Call e; e.funcs = Funcs(NQE_MAX_WINDOW_FUNCS + 1, nqe_window_spec{NQE_WIN_SUM, 99, 1});
+        CHECK(status(e, &msg) == NQE_ERR_NOT_SUPPORTED && msg.find("at most 16 window functions") != std::string::npos);
+        Call f; f.parts = std::vector<int32_t>(NQE_MAX_WINDOW_KEYS, I); f.order = Keys(NQE_MAX_WINDOW_KEYS, nqe_sort_key{S, 1, 0}); f.funcs = Funcs(NQE_MAX_WINDOW_FUNCS, nqe_window_spec{NQE_WIN_SUM, F, 1});
+        CHECK(status(f) == NQE_OK);
+    }
+    // 5. a key or value column index out of range — before the dtypes
+    for (int32_t bad : {-1, int32_t(NCOLS)}) {
+        Call c; c.parts = {I, bad}; c.funcs = {{NQE_WIN_SUM, S, 1}};
+        CHECK(status(c, &msg) == NQE_ERR_NOT_SUPPORTED && msg == "window: key column index out of range");
+        Call d; d.order = {{bad, 0, 1}}; d.parts = {NONE};
+        CHECK(status(d, &msg) == NQE_ERR_NOT_SUPPORTED && msg == "window: key column index out of range");
+        Call e; e.funcs = {{NQE_WIN_RANK, 0, 0}, {NQE_WIN_MAX, bad, 0}}; e.parts = {NONE};
+        CHECK(status(e, &msg) == NQE_ERR_NOT_SUPPORTED && msg == "aggregate column index out of range");
+    }
+    // 6. a key dtype the sort refuses — before the aggregates' dtypes
+    {
+        Call c; c.parts = {NONE}; c.funcs = {{NQE_WIN_SUM, S, 1}};
+        CHECK(status(c, &msg) == NQE_ERR_NOT_SUPPORTED && msg == "order by: keys of this type are not implemented");
+        Call d; d.order = {{I, 0, 1}, {NONE, 1, 0}};
+        CHECK(status(d, &msg) == NQE_ERR_NOT_SUPPORTED && msg == "order by: keys of this type are not implemented");
+        Call e; e.parts = {I, U, F, B, S}; e.order = {{S, 1, 0}, {B, 0, 1}};
+        CHECK(status(e) == NQE_OK);
+    }
+    // 7. an aggregate over Boolean or Utf8 (check_aggregates' message) — before the row count
+    for (int f = NQE_WIN_COUNT; f <= NQE_WIN_AVG; ++f)
+        for (int32_t col : {int32_t(B), int32_t(S), int32_t(NONE)}) {
+            Call c; c.funcs = {{NQE_WIN_SUM, F, 0}, {f, col, 2}}; c.rows = int64_t(1) << 32;
+            CHECK(status(c, &msg) == NQE_ERR_NOT_SUPPORTED && msg == "aggregate func for this column type is not supported");
+        }
+    // 8. 2^32 rows or more
+    {
+        Call c; c.rows = int64_t(1) << 32;
+        CHECK(status(c, &msg) == NQE_ERR_NOT_SUPPORTED && msg.find("4294967296 rows, the sort handles fewer than 2^32") != std::string::npos);
+        c.rows = (int64_t(1) << 32) - 1;
+        CHECK(status(c) == NQE_OK);
+        c.rows = 0;
+        CHECK(status(c) == NQE_OK);
+    }
+}
+
+static void test_plan() {
+    Call c;
+    c.parts = {S, I};
+    c.order = {{F, 1, 0}, {I, 0, 1}};
+    c.funcs = {{NQE_WIN_SUM, F, NQE_FRAME_ROWS},      {NQE_WIN_ROW_NUMBER, 77, 77}, {NQE_WIN_AVG, U, NQE_FRAME_RANGE}, {NQE_WIN_MIN, F, NQE_FRAME_PARTITION},
+               {NQE_WIN_COUNT, F, NQE_FRAME_ROWS},    {NQE_WIN_MAX, I, NQE_FRAME_ROWS},  {NQE_WIN_MAX, F, NQE_FRAME_RANGE}, {NQE_WIN_DENSE_RANK, 0, 0}};
+    WindowPlan p;
+    CHECK(status(c, nullptr, &p) == NQE_OK);
+    // the distinct value columns in order of first appearance, each with the operators its functions need
+    CHECK((p.val_cols == std::vector<int32_t>{F, U, I}));
+    CHECK((p.val_ops == std::vector<int>{WIN_OP_SUM | WIN_OP_MIN | WIN_OP_COUNT | WIN_OP_MAX, WIN_OP_SUM | WIN_OP_COUNT, WIN_OP_MAX}));
+    CHECK((p.slot == std::vector<int>{0, -1, 1, 0, 0, 2, 0, -1}));
+    CHECK(p.positions == (WIN_POS_PART_FIRST | WIN_POS_PEER_COUNT | WIN_POS_PEER_LAST | WIN_POS_PART_LAST));
+    // the sorted order: the partition keys with default options, then the order keys as given
+    CHECK(p.sort_keys.size() == 4);
+    const nqe_sort_key want[4] = {{S, 0, 1}, {I, 0, 1}, {F, 1, 0}, {I, 0, 1}};
+    for (size_t k = 0; k < 4 && k < p.sort_keys.size(); ++k)
+        CHECK(p.sort_keys[k].column == want[k].column && p.sort_keys[k].descending == want[k].descending && p.sort_keys[k].nulls_first == want[k].nulls_first);
+
+    Call r; r.funcs = {{NQE_WIN_RANK, 0, 0}};
+    CHECK(status(r, nullptr, &p) == NQE_OK && p.val_cols.empty() && p.positions == (WIN_POS_PART_FIRST | WIN_POS_PEER_FIRST) && p.sort_keys.empty());
+    Call rows_only; rows_only.funcs = {{NQE_WIN_SUM, I, NQE_FRAME_ROWS}};
+    CHECK(status(rows_only, nullptr, &p) == NQE_OK && p.positions == 0 && p.val_ops == std::vector<int>{WIN_OP_SUM});
+    CHECK(win_ops_of(NQE_WIN_COUNT) == WIN_OP_COUNT && win_ops_of(NQE_WIN_AVG) == (WIN_OP_SUM | WIN_OP_COUNT) && win_ops_of(NQE_WIN_RANK) == 0);
+}
+
+static void test_tiles() {
+    static_assert(WIN_TILE == int64_t(WIN_THREADS) * WIN_ITEMS, "a tile is one workgroup's rows");
+    const int64_t T = WIN_TILE, last = (int64_t(1) << 32) - 1;
+    struct { int64_t n, tiles; } want[] = {{0, 0}, {1, 1}, {T - 1, 1}, {T, 1}, {T + 1, 2}, {last, (last + T - 1) / T}};
+    for (auto &w : want) {
+        CHECK(win_tiles(w.n) == w.tiles);
+        CHECK(win_padded_rows(w.n) == w.tiles * T && win_padded_rows(w.n) >= w.n && win_padded_rows(w.n) - w.n < T);
+        CHECK(win_carry_chunks(w.n) == (w.tiles + WIN_THREADS - 1) / WIN_THREADS);
+    }
+    CHECK(win_tiles(last) == 1048576 && win_carry_chunks(last) == 4096 && win_carry_chunks(T + 1) == 1 && win_carry_chunks(0) == 0);
+    CHECK(win_tiles(100000000) == 24415); // 10^8 rows: about 24 K carries
+}
+
+int main() {
+    test_errors_in_order();
+    test_plan();
+    test_tiles();
+    if (failures) {
+        std::printf("%d checks failed\n", failures);
+        return 1;
+    }
+    std::printf("window plan ok\n");
+    return 0;
+}

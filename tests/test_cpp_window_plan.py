@@ -1,0 +1,15 @@
+"""The host analysis of the window operator (naive_query_engine_amd/csrc/window_plan.hpp: the argument checks in their order, the
+distinct value columns and their scan operators, the position arrays, the tile and carry counts) on the CPU:
+tests/cpp/test_window_plan.cpp includes that header alone, is compiled with g++ and run."""
+import os
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_window_plan(tmp_path):
+    exe = str(tmp_path / "test_window_plan")
+    src = os.path.join(ROOT, "tests", "cpp", "test_window_plan.cpp")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-Wno-unused-function", "-I", os.path.join(ROOT, "naive_query_engine_amd", "csrc"), src, "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0 and "window plan ok" in out.stdout, out.stdout + out.stderr
