@@ -3046,9 +3046,11 @@ def test_aggregate_block_scatter_forms(ctx, shape):
 
 @pytest.mark.parametrize("tiles", [1, 4095, 4096, 4097, 8193, 24575, 24576, 24577, 30001])
 def test_selection_tile_offsets_across_the_scan_forms(ctx, tiles):
-    """The tile counts of a selection are scanned by ONE workgroup up to 6 x 4096 tiles (every thread 24 consecutive counts, one wave scan:
-    round 6) and by the chunked recursive scan beyond: row counts around every boundary, ragged last tiles, kept rows checked against numpy
-    (count, every kept value through a checksum, first and last).  selection.rs:58-107"""
+    """The tile counts of a selection are scanned into a buffer of their own, so sort.hip's scan_impl takes them by chunks of 4096: one
+    chunk by scan_chunk alone, 2 to 32 chunks by scan_redundant_kernel (one workgroup per chunk, each adding up what lies in front of its
+    chunk itself), and only from 33 chunks on by the chunked recursive scan (scan_chunk, the scan of the chunk sums, scan_add).  The
+    one-workgroup scan_single_kernel takes 2 to 8 chunks only when a scan runs in place, which a selection's does not.  Row counts around
+    the chunk boundaries up to 8 chunks, ragged last tiles, every kept row checked against numpy.  selection.rs:58-107"""
     rng = np.random.default_rng(tiles)
     n = tiles * 4096 - int(rng.integers(0, 4095)) if tiles > 1 else 1234
     ids = rng.integers(0, 1000, n).astype(np.int64)

@@ -18,14 +18,18 @@ The functions:
                  frame one group, and tests/test_window_model.py holds the two against each other
 The comparator (assert_matches_window): ranking, count, min, max equal (every NaN equals every NaN, +0.0 equals -0.0 for min / max);
 sum and avg within the bound (avg: the bound over the count plus one ulp of the quotient).  No case is left out and there is no
-relative tolerance."""
+relative tolerance.
+
+window_np is the same model in whole-array numpy steps, for the tables of 10^6 rows of tests/test_gpu_window_sizes.py (a narrower value
+domain, on which every sum is exact); layout_lengths / layout_table build those tables.  tests/test_large_models_host.py holds window_np
+against window."""
 import math
 
 import numpy as np
 
 import agg_value_util as avu
 import order_by_util as obu
-from naive_query_engine_amd import DType, WindowFrame, WindowFunc
+from naive_query_engine_amd import Column, DType, WindowFrame, WindowFunc
 
 RANKING = (WindowFunc.RowNumber, WindowFunc.Rank, WindowFunc.DenseRank)
 AGGREGATES = (WindowFunc.Count, WindowFunc.Sum, WindowFunc.Min, WindowFunc.Max, WindowFunc.Avg)
@@ -190,6 +194,180 @@ def window(cols, partition_by, order_by, funcs):
         out_cols.append(vals)
         out_tols.append(tol)
     return ModelWindow(funcs, out_cols, out_tols)
+
+
+# ----------------------------------------------------------------------------- the same model, vectorised
+NP_VALUE_LIMIT = 2 ** 20   # window_np: finite values are integers of smaller magnitude
+_INF_KEY = NP_VALUE_LIMIT + 1   # +inf / -inf as integers beyond every finite value
+_NONE_KEY = NP_VALUE_LIMIT + 2  # "no value yet": the start values F64_MAX (min) and -F64_MAX (max)
+_BIG = 4 * _NONE_KEY           # more than the distance between any two keys: the offset between two partitions
+
+
+def _since_partition_start(x, part_first):
+    """per position: the sum of x over its partition's positions up to and including it (int64: exact)"""
+    c = np.cumsum(x, dtype=np.int64)
+    return c - (c[part_first] - x[part_first])
+
+
+def _running_extreme(key, pidx, largest, partition_offset=True):
+    """per position: the smallest (largest) key of its partition up to and including it.  Partition p's keys are moved by p * _BIG away
+    from those of every earlier partition, in the direction the accumulation prefers, so one pass over the table never carries a value
+    across a partition start.  (partition_offset=False is the WRONG variant tests/test_large_models_host.py must tell apart.)"""
+    off = pidx * _BIG if partition_offset else np.zeros_like(pidx)
+    return np.maximum.accumulate(key + off) - off if largest else np.minimum.accumulate(key - off) + off
+
+
+def _key_to_f64(k):
+    out = k.astype(np.float64)
+    out[k == _INF_KEY], out[k == -_INF_KEY] = np.inf, -np.inf
+    out[k == _NONE_KEY], out[k == -_NONE_KEY] = avu.F64_MAX, -avu.F64_MAX
+    return out
+
+
+def window_np(cols, partition_by, order_by, funcs, _partition_offset=True):
+    """`window` in whole-array numpy steps, fast enough for 10^6 rows.  Defined for value columns whose finite values are integers of
+    magnitude < 2^20 (Int64, or Float64 with +-inf, NaN anywhere), NULLs anywhere, fewer than 2^32 rows.  Every frame's sum is then an
+    integer below 2^53: every order of the additions gives it exactly, so the bound of sum is 0 and avg's one ulp of the quotient.
+    tests/test_large_models_host.py holds it against `window`."""
+    funcs = normalise_funcs(funcs)
+    n = cols[0].length if cols else 0
+    keys = [(int(c), False, True) for c in partition_by] + obu.normalise_keys(order_by)
+    order = obu.sort_indices_np(cols, keys)
+    idx = np.arange(n, dtype=np.int64)
+    # starts: a sorted position whose row differs from the row before it on a partition key (on any key: a peer start)
+    part_start, peer_start = idx == 0, idx == 0
+    for k, arrs in enumerate(obu.key_arrays(cols, keys)):
+        for a in arrs:
+            s = a[order]
+            differs = np.concatenate([[True], s[1:] != s[:-1]]) if n else np.zeros(0, dtype=bool)
+            peer_start = peer_start | differs
+            if k < len(partition_by):
+                part_start = part_start | differs
+    part_first = np.maximum.accumulate(np.where(part_start, idx, 0))
+    peer_first = np.maximum.accumulate(np.where(peer_start, idx, 0))
+    # the mirror: the nearest start AFTER a position, less one; none: the last position
+    nearest = lambda start: np.minimum.accumulate(np.where(start, idx, n)[::-1])[::-1]
+    part_last = np.concatenate([nearest(part_start)[1:], [n]])[:n] - 1
+    peer_last = np.concatenate([nearest(peer_start)[1:], [n]])[:n] - 1
+    dense = np.cumsum(peer_start, dtype=np.int64)
+    pidx = np.cumsum(part_start, dtype=np.int64) - 1
+    ends = {WindowFrame.Rows: idx, WindowFrame.Range: peer_last, WindowFrame.Partition: part_last}
+
+    states = {}
+
+    def state(c):
+        """per sorted position, over its partition's rows up to and including it: count, sum, min, max"""
+        if c not in states:
+            assert cols[c].dtype in (DType.INT64, DType.UINT64, DType.FLOAT64)
+            x = cols[c].to_numpy().astype(np.float64)[order]
+            ok = cols[c].valid_mask()[order]
+            nan, fin = ok & np.isnan(x), ok & np.isfinite(x)
+            if not ((np.abs(x[fin]) < NP_VALUE_LIMIT).all() and (x[fin] == np.round(x[fin])).all()):
+                raise ValueError("window_np: a finite value is no integer of magnitude < 2^20; use window")
+            v = np.where(fin, x, 0.0).astype(np.int64)
+            since = lambda a: _since_partition_start(a.astype(np.int64), part_first)
+            count, total = since(ok), since(v).astype(np.float64)
+            any_nan, pinf, ninf = since(nan) > 0, since(ok & (x == np.inf)) > 0, since(ok & (x == -np.inf)) > 0
+            total = np.where(any_nan | (pinf & ninf), np.nan, np.where(pinf, np.inf, np.where(ninf, -np.inf, total)))
+            key = np.where(x == np.inf, _INF_KEY, np.where(x == -np.inf, -_INF_KEY, v))
+            # (Q10: min starts at F64_MAX and max at -F64_MAX, so +inf never shows in a min nor -inf in a max)
+            mn = _key_to_f64(_running_extreme(np.where(ok & ~nan & (x != np.inf), key, _NONE_KEY), pidx, False, _partition_offset))  # min skips a NaN
+            mx = _key_to_f64(_running_extreme(np.where(ok & ~nan & (x != -np.inf), key, -_NONE_KEY), pidx, True, _partition_offset))
+            states[c] = count, total, mn, np.where(any_nan, np.nan, mx)                                              # max keeps it
+        return states[c]
+
+    out_cols, out_tols = [], []
+    for fn, c, frame in funcs:
+        tol = None
+        if fn in RANKING:
+            sorted_vals = {WindowFunc.RowNumber: idx - part_first + 1, WindowFunc.Rank: peer_first - part_first + 1,
+                           WindowFunc.DenseRank: dense - dense[part_first] + 1}[fn].astype(np.uint64)
+        else:
+            count, total, mn, mx = (a[ends[frame]] for a in state(c))
+            if fn == WindowFunc.Count:
+                sorted_vals = count.astype(np.uint64)
+            elif fn == WindowFunc.Min:
+                sorted_vals = mn
+            elif fn == WindowFunc.Max:
+                sorted_vals = mx
+            else:
+                sorted_vals, sorted_tol = total, np.zeros(n, dtype=np.float64)
+                if fn == WindowFunc.Avg:
+                    with np.errstate(invalid="ignore", divide="ignore"):
+                        sorted_vals = total / count.astype(np.float64)
+                        fin = np.isfinite(sorted_vals)
+                        sorted_tol = np.where(fin, np.spacing(np.abs(np.where(fin, sorted_vals, 0.0))), 0.0)
+                tol = np.zeros(n, dtype=np.float64)
+                tol[order] = sorted_tol
+        vals = np.zeros(n, dtype=sorted_vals.dtype)
+        vals[order] = sorted_vals
+        out_cols.append(vals)
+        out_tols.append(tol)
+    return ModelWindow(funcs, out_cols, out_tols)
+
+
+# ----------------------------------------------------------------------------- partition layouts by explicit lengths
+LAYOUTS = ("one_partition", "tile_edges", "flagless_chunk", "every_row_its_own", "random_lengths")
+
+
+def layout_lengths(name, n, tile, chunk, rng=None, inside=5000, longest=10_000):
+    """the partition lengths of one layout over n rows, in built order.  `tile`: the rows of one scan tile; `chunk`: the rows of the
+    tiles ONE trip of the carry scans covers.
+      one_partition      the running state crosses every tile and chunk
+      tile_edges         a start on the last row of the tile in front of the first chunk edge and one on the first row behind it
+                         (fewer rows than a chunk: at the edge of the middle tile)
+      flagless_chunk     one partition from `inside` rows in front of the first chunk edge to the middle of what lies behind the second:
+                         the chunk between holds no start at all (no more than two chunks of rows: the same over thirds of the tiles)
+      every_row_its_own  n partitions
+      random_lengths     seeded lengths between 1 and `longest`"""
+    if n == 0:
+        return []
+    tiles = (n + tile - 1) // tile
+    if name == "one_partition":
+        lengths = [n]
+    elif name == "tile_edges":
+        edge = chunk if n >= chunk else max(1, tiles // 2) * tile
+        lengths = [edge - 1, 1, n]
+    elif name == "flagless_chunk":
+        c = chunk if n > 2 * chunk else max(1, tiles // 3) * tile
+        a, tail = min(inside, max(1, c // 4)), max(0, n - 2 * c)
+        lengths = [c - a, a + c + tail // 2, max(1, (tail - tail // 2) // 2), n]
+    elif name == "every_row_its_own":
+        return [1] * n
+    else:
+        assert name == "random_lengths"
+        lengths = rng.integers(1, longest, n // max(1, longest // 2) + 8, endpoint=True).tolist() + [n]
+    out, left = [], n   # cut the list off at n rows
+    for length in lengths:
+        length = min(int(length), left)
+        if length > 0:
+            out.append(length)
+            left -= length
+    assert sum(out) == n
+    return out
+
+
+def layout_table(lengths, rng, peers_of_three, poisoned=None):
+    """(columns in built order, partition keys, order keys): column 0 the partition number, column 1 the order key — the built position,
+    so the sorted order is the built order, or a third of it: peer groups of three that straddle whatever edge the lengths straddle —,
+    column 2 Int64 in (-2^20, 2^20) with about 10 % NULLs, column 3 Float64 with integer values of that range.  In the partition
+    `poisoned` every third row of column 3 is +inf, -inf or NaN in turn (the cancellation trap: "the prefix at the row minus the prefix
+    at the partition's start" gives NaN for every later partition)."""
+    n = int(np.sum(lengths)) if len(lengths) else 0
+    part = np.repeat(np.arange(len(lengths), dtype=np.int64), lengths)
+    pos = np.arange(n, dtype=np.int64)
+    v = rng.integers(-NP_VALUE_LIMIT + 1, NP_VALUE_LIMIT, n).astype(np.int64)
+    x = rng.integers(-NP_VALUE_LIMIT + 1, NP_VALUE_LIMIT, n).astype(np.float64)
+    if poisoned is not None and n:
+        rows = np.nonzero(part == poisoned)[0]
+        x[rows[::9]], x[rows[3::9]], x[rows[6::9]] = np.inf, -np.inf, np.nan
+    cols = [Column.from_numpy(part), Column.from_numpy(pos // 3 if peers_of_three else pos), Column.from_numpy(v, rng.random(n) > 0.1), Column.from_numpy(x)]
+    return cols, [0], [1]
+
+
+def split_model(model, lo, hi):
+    """the ModelWindow of functions [lo, hi) of a call (one call takes at most 16 functions; the model is computed once)"""
+    return ModelWindow(model.funcs[lo:hi], model.cols[lo:hi], model.tols[lo:hi])
 
 
 # ----------------------------------------------------------------------------- the comparator
