@@ -794,6 +794,50 @@ nqe_status nqe_window_execute(nqe_ctx *ctx, const nqe_table *in, const int32_t *
                               const nqe_sort_key *order_keys, int32_t num_order, const nqe_window_spec *funcs,
                               int32_t num_funcs, nqe_table **out);
 
+/* ------------------------------------------------------------------ DISTINCT and the set operators
+ * SELECT DISTINCT, UNION, INTERSECT and EXCEPT — quirk Q24: the reference has none of them (its
+ * JoinType is {Inner, Left, Right, Cross} and its SQL planner knows no DISTINCT and no set
+ * operator), so the definition is this project's.
+ * TUPLE EQUALITY is the sort's and the window's tie, per key column: Int64 / UInt64 the 64-bit
+ * word, Float64 as OrderedFloat (-0.0 = +0.0, every NaN equals every NaN), Boolean the bit, Utf8
+ * byte for byte; a NULL equals a NULL, whatever lies under it, and differs from every value; the
+ * empty string is a value, not NULL.  Tuples compare position by position: ("a","b") differs
+ * from ("ab",""), (1,2) from (2,1).  (The semi and anti joins keep the hash join's relation, Q11:
+ * they ignore validity.  This operator does the opposite.)
+ * nqe_distinct_execute: the rows of `in` that are the FIRST occurrence (smallest row index) of
+ * their tuple over the key columns `cols`, in input order, with every column of `in` taken from
+ * that row — payload columns outside `cols` too.  num_cols == 0 with cols == NULL: every column
+ * is a key (SELECT DISTINCT *).  Output columns are the selection's compaction of their source:
+ * validity preserved, null_count exact, the first row's own bits kept (-0.0 stays -0.0 when it
+ * came first).  The result is the same on every run.
+ * nqe_set_op_execute: every column is a key; both tables need the same number of columns and the
+ * same dtype at every position; neither needs to be duplicate-free.  INTERSECT: the rows of
+ * distinct(left) whose tuple occurs in `right`; EXCEPT: the rest — the two partition
+ * distinct(left), each in left's order with left's bits and validity.  UNION:
+ * distinct(nqe_table_concat(left, right)) bit for bit: left's distinct rows in order, then
+ * right's rows not seen before, in order.
+ * Errors, all before any launch or allocation, in this order: (1) NULL ctx / in / left / right /
+ * out, cols == NULL with num_cols > 0, op outside its enum NQE_ERR_INVALID_ARGUMENT; (2) set op
+ * only: a differing column count, then the first differing dtype in column order NQE_ERR_PLAN;
+ * (3) num_cols < 0 or more than NQE_MAX_SET_KEYS key columns NQE_ERR_NOT_SUPPORTED; (4) a key
+ * index out of range or given twice NQE_ERR_NOT_SUPPORTED (then: a key of dtype NQE_NULLTYPE
+ * NQE_ERR_NOT_SUPPORTED, zero columns with zero keys NQE_ERR_PLAN); (5) 2^31 rows or more in the
+ * table that is inserted — `in`, `left`, for UNION both together — NQE_ERR_NOT_SUPPORTED; the
+ * probed `right` of INTERSECT / EXCEPT has no such limit.  Table memory that cannot be had:
+ * NQE_ERR_OUT_OF_MEMORY.  UNION's concatenation reports what nqe_table_concat reports.  Zero rows
+ * give a 0-row table with every column.  Nothing is kept between calls.
+ * Out of scope: INTERSECT ALL and EXCEPT ALL (multiplicities); count(distinct x); DISTINCT over
+ * expressions (the host mirrors make temporary columns, as the window plan does); SQL parsing;
+ * sharded forms. */
+#define NQE_MAX_SET_KEYS 32
+typedef enum nqe_set_op {
+    NQE_SET_UNION = 0,
+    NQE_SET_INTERSECT = 1,
+    NQE_SET_EXCEPT = 2
+} nqe_set_op;
+nqe_status nqe_distinct_execute(nqe_ctx *ctx, const nqe_table *in, const int32_t *cols, int32_t num_cols, nqe_table **out);
+nqe_status nqe_set_op_execute(nqe_ctx *ctx, const nqe_table *left, const nqe_table *right, int32_t op, nqe_table **out);
+
 /* ------------------------------------------------------------------ take
  * arrow::compute::take(array, &Int64Array indices, None) over every column
  * (hash_join.rs:239,245): out[j] = in[indices[j]]; `indices` = Int64 column `idx_column` of

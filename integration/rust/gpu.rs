@@ -79,6 +79,8 @@ pub struct NqeWindowSpec { pub func: i32, pub column: i32, pub frame: i32 }
 pub const NQE_WIN_ROW_NUMBER: i32 = 0; pub const NQE_WIN_RANK: i32 = 1; pub const NQE_WIN_DENSE_RANK: i32 = 2; pub const NQE_WIN_COUNT: i32 = 3;
 pub const NQE_WIN_SUM: i32 = 4; pub const NQE_WIN_MIN: i32 = 5; pub const NQE_WIN_MAX: i32 = 6; pub const NQE_WIN_AVG: i32 = 7;
 pub const NQE_FRAME_PARTITION: i32 = 0; pub const NQE_FRAME_ROWS: i32 = 1; pub const NQE_FRAME_RANGE: i32 = 2;
+// nqe_set_op (quirk Q24)
+pub const NQE_SET_UNION: i32 = 0; pub const NQE_SET_INTERSECT: i32 = 1; pub const NQE_SET_EXCEPT: i32 = 2;
 pub enum NqeCtx {}
 pub enum NqeTable {}
 pub enum NqeJoinTable {}
@@ -139,6 +141,8 @@ extern "C" {
     fn nqe_sort_execute(ctx: *mut NqeCtx, input: *const NqeTable, keys: *const NqeSortKey, num_keys: i32, fetch: i64, out: *mut *mut NqeTable) -> i32;
     fn nqe_window_execute(ctx: *mut NqeCtx, input: *const NqeTable, partition_cols: *const i32, num_partition: i32, order_keys: *const NqeSortKey, num_order: i32,
                           funcs: *const NqeWindowSpec, num_funcs: i32, out: *mut *mut NqeTable) -> i32;
+    fn nqe_distinct_execute(ctx: *mut NqeCtx, input: *const NqeTable, cols: *const i32, num_cols: i32, out: *mut *mut NqeTable) -> i32;
+    fn nqe_set_op_execute(ctx: *mut NqeCtx, left: *const NqeTable, right: *const NqeTable, op: i32, out: *mut *mut NqeTable) -> i32;
 }
 
 // ------------------------------------------------------------------ context, device tables, upload, download
@@ -1015,6 +1019,58 @@ impl PhysicalPlan for GpuWindowPlan {
     fn as_gpu(&self) -> Option<&dyn GpuExec> { Some(self) }
 }
 
+/// SELECT DISTINCT (quirk Q24: the reference's planner has no DISTINCT): the input batches are concatenated and ONE batch with the input's
+/// schema leaves — the rows that are the first occurrence of their tuple over the key columns `cols` (None: every column), in input
+/// order.  NULL = NULL, -0.0 = +0.0, every NaN one value.  A front end that plans DISTINCT creates it directly.
+#[derive(Debug)]
+pub struct GpuDistinctPlan { input: PhysicalPlanRef, cols: Option<Vec<i32>>, ctx: Arc<GpuCtx> }
+impl GpuDistinctPlan {
+    pub fn create(ctx: Arc<GpuCtx>, input: PhysicalPlanRef, cols: Option<Vec<i32>>) -> PhysicalPlanRef { Arc::new(Self { input, cols, ctx }) }
+}
+impl GpuExec for GpuDistinctPlan {
+    fn execute_device(&self) -> Result<Vec<GpuBatch>> {
+        let batches = child_device(&self.ctx, &self.input)?;
+        if batches.is_empty() { return Err(ErrorCode::NotSupported("distinct over an empty batch list is not supported on the device path".to_string())); }
+        let all = self.ctx.concat(&batches)?;
+        let mut t = std::ptr::null_mut();
+        let (ptr, n) = match &self.cols { Some(c) => (c.as_ptr(), c.len() as i32), None => (std::ptr::null(), 0) };
+        self.ctx.check(unsafe { nqe_distinct_execute(self.ctx.0, all.table.0, ptr, n, &mut t) })?;
+        Ok(vec![GpuBatch::wrap(t)])
+    }
+}
+impl PhysicalPlan for GpuDistinctPlan {
+    fn schema(&self) -> &NaiveSchema { self.input.schema() }
+    fn children(&self) -> Result<Vec<PhysicalPlanRef>> { Ok(vec![self.input.clone()]) }
+    fn execute(&self) -> Result<Vec<RecordBatch>> { self.ctx.download_all(&self.execute_device()?, self.schema()) }
+    fn as_any(&self) -> &dyn Any { self }
+    fn as_gpu(&self) -> Option<&dyn GpuExec> { Some(self) }
+}
+
+/// UNION / INTERSECT / EXCEPT (quirk Q24: the reference's planner has no set operator; `op` is NQE_SET_*): every column is a key and
+/// both inputs need the same column types.  The batches of each side are concatenated and ONE batch with left's schema leaves.
+#[derive(Debug)]
+pub struct GpuSetOpPlan { left: PhysicalPlanRef, right: PhysicalPlanRef, op: i32, ctx: Arc<GpuCtx> }
+impl GpuSetOpPlan {
+    pub fn create(ctx: Arc<GpuCtx>, left: PhysicalPlanRef, right: PhysicalPlanRef, op: i32) -> PhysicalPlanRef { Arc::new(Self { left, right, op, ctx }) }
+}
+impl GpuExec for GpuSetOpPlan {
+    fn execute_device(&self) -> Result<Vec<GpuBatch>> {
+        let (lb, rb) = (child_device(&self.ctx, &self.left)?, child_device(&self.ctx, &self.right)?);
+        if lb.is_empty() || rb.is_empty() { return Err(ErrorCode::NotSupported("a set operation over an empty batch list is not supported on the device path".to_string())); }
+        let (l, r) = (self.ctx.concat(&lb)?, self.ctx.concat(&rb)?);
+        let mut t = std::ptr::null_mut();
+        self.ctx.check(unsafe { nqe_set_op_execute(self.ctx.0, l.table.0, r.table.0, self.op, &mut t) })?;
+        Ok(vec![GpuBatch::wrap(t)])
+    }
+}
+impl PhysicalPlan for GpuSetOpPlan {
+    fn schema(&self) -> &NaiveSchema { self.left.schema() }
+    fn children(&self) -> Result<Vec<PhysicalPlanRef>> { Ok(vec![self.left.clone(), self.right.clone()]) }
+    fn execute(&self) -> Result<Vec<RecordBatch>> { self.ctx.download_all(&self.execute_device()?, self.schema()) }
+    fn as_any(&self) -> &dyn Any { self }
+    fn as_gpu(&self) -> Option<&dyn GpuExec> { Some(self) }
+}
+
 /// PhysicalLimitPlan / PhysicalOffsetPlan (limit.rs:32-49, offset.rs:30-51) over device batches: whole batches are passed on,
 /// a cut batch is nqe_table_slice — so a LIMIT above a device operator downloads `n` rows, not the operator's whole result
 #[derive(Debug)]
@@ -1131,6 +1187,12 @@ pub fn rewrite_sharded(ctx: &Arc<GpuCtx>, comm: Option<&Arc<GpuComm>>, plan: Phy
     }
     if let Some(w) = any.downcast_ref::<GpuWindowPlan>() { // keeps its operator, with a rewritten child (a limit above it stays a limit)
         return Ok(GpuWindowPlan::create(ctx.clone(), rewrite(ctx, w.input.clone())?, w.partition_by.clone(), w.order_by.clone(), w.funcs.clone(), w.names.clone()));
+    }
+    if let Some(d) = any.downcast_ref::<GpuDistinctPlan>() { // quirk Q24: the node stays, its child is rewritten
+        return Ok(GpuDistinctPlan::create(ctx.clone(), rewrite(ctx, d.input.clone())?, d.cols.clone()));
+    }
+    if let Some(s) = any.downcast_ref::<GpuSetOpPlan>() {
+        return Ok(GpuSetOpPlan::create(ctx.clone(), rewrite(ctx, s.left.clone())?, rewrite(ctx, s.right.clone())?, s.op));
     }
     if let Some(o) = any.downcast_ref::<PhysicalOffsetPlan>() {
         return Ok(GpuLimitPlan::create_offset(ctx.clone(), rewrite(ctx, o.input.clone())?, o.n));

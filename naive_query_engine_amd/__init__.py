@@ -12,14 +12,14 @@ Layout:
   rewrite.py       plan rewrite pass (unfused reference-shaped tree → fused device operators), Catalog / NaiveDB surface
   parallel.py      row-range sharding across GPUs: thin caller of the C ABI's sharded entry points (RCCL)
 """
-from .arrow_host import (AggregateFunc, Column, DType, ErrorCode, Field, Operator, RecordBatch, ScalarValue, Status,
+from .arrow_host import (AggregateFunc, Column, DType, ErrorCode, Field, Operator, RecordBatch, ScalarValue, SetOp, Status,
                          UnaryOperator, WindowFrame, WindowFunc, read_csv)
 from .expression import ColumnExpr, PhysicalBinaryExpr, PhysicalExpr, PhysicalLiteralExpr, PhysicalUnaryExpr
 
 __all__ = [
     "AggregateFunc", "Column", "DType", "ErrorCode", "Field", "Operator", "RecordBatch", "ScalarValue", "Status",
     "read_csv", "ColumnExpr", "PhysicalBinaryExpr", "PhysicalExpr", "PhysicalLiteralExpr", "PhysicalUnaryExpr", "UnaryOperator",
-    "WindowFrame", "WindowFunc",
+    "WindowFrame", "WindowFunc", "SetOp",
 ]
 
 

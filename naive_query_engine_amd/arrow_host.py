@@ -96,6 +96,14 @@ class WindowFrame(enum.IntEnum):
     Range = 2
 
 
+class SetOp(enum.IntEnum):
+    """nqe_set_op (include/nqe.h; quirk Q24: the reference has no set operator)"""
+
+    Union = 0
+    Intersect = 1
+    Except = 2
+
+
 class Status(enum.IntEnum):
     """nqe_status; 1..13 mirror enum ErrorCode (src/error.rs:13-40)."""
 

@@ -29,7 +29,7 @@ SYMBOLS = [
     "nqe_filter", "nqe_selection_execute", "nqe_projection_execute", "nqe_selection_projection_execute",
     "nqe_aggregate_execute", "nqe_aggregate_partial", "nqe_aggregate_merge", "nqe_aggregate_merge_packed", "nqe_group_aggregate_execute", "nqe_hash_join_execute",
     "nqe_hash_join_build", "nqe_hash_join_probe", "nqe_join_table_release", "nqe_join_marks_create", "nqe_join_marks_release",
-    "nqe_hash_join_probe_outer", "nqe_hash_join_unmatched_build", "nqe_hash_join_build_keys", "nqe_hash_join_probe_keys", "nqe_hash_join_execute_keys", "nqe_hash_join_probe_semi", "nqe_hash_join_marked_build", "nqe_cross_join_execute", "nqe_nested_loop_join_execute", "nqe_sort_execute", "nqe_window_execute", "nqe_take", "nqe_synth_fill",
+    "nqe_hash_join_probe_outer", "nqe_hash_join_unmatched_build", "nqe_hash_join_build_keys", "nqe_hash_join_probe_keys", "nqe_hash_join_execute_keys", "nqe_hash_join_probe_semi", "nqe_hash_join_marked_build", "nqe_cross_join_execute", "nqe_nested_loop_join_execute", "nqe_sort_execute", "nqe_window_execute", "nqe_distinct_execute", "nqe_set_op_execute", "nqe_take", "nqe_synth_fill",
     "nqe_device_alloc", "nqe_device_free",
     "nqe_comm_get_unique_id", "nqe_comm_rccl_version", "nqe_comm_create", "nqe_comm_create_custom", "nqe_comm_create_p2p", "nqe_comm_destroy", "nqe_comm_rank",
     "nqe_comm_world", "nqe_table_all_gather", "nqe_sharded_aggregate_execute", "nqe_sharded_hash_join_probe",
@@ -155,6 +155,8 @@ def lib():
         "nqe_nested_loop_join_execute": (i32, [vp, vp, vp, i32, i32, pvp]),
         "nqe_sort_execute": (i32, [vp, vp, C.POINTER(NqeSortKey), i32, i64, pvp]),
         "nqe_window_execute": (i32, [vp, vp, C.POINTER(i32), i32, C.POINTER(NqeSortKey), i32, C.POINTER(NqeWindowSpec), i32, pvp]),
+        "nqe_distinct_execute": (i32, [vp, vp, C.POINTER(i32), i32, pvp]),
+        "nqe_set_op_execute": (i32, [vp, vp, vp, i32, pvp]),
         "nqe_take": (i32, [vp, vp, vp, i32, pvp]),
         "nqe_synth_fill": (i32, [vp, i32, u64, i64, i64, u64, i64, vp]),
         "nqe_device_alloc": (i32, [vp, C.c_size_t, pvp]),
@@ -524,6 +526,25 @@ class Context:
         farr = (NqeWindowSpec * max(1, len(fs)))(*[NqeWindowSpec(int(f), 0 if c is None else int(c), 2 if fr is None else int(fr)) for f, c, fr in fs])
         h = C.c_void_p()
         self.check(lib().nqe_window_execute(self.handle, table.handle, parr, len(parts), karr, len(ks), farr, len(fs), C.byref(h)))
+        return Table(self, h)
+
+    def distinct(self, table: "Table", cols=None) -> "Table":
+        """SELECT DISTINCT over one table (quirk Q24): the rows that are the first occurrence of their tuple over the key columns `cols`
+        (None: every column), in input order, with every column of `table`; NULL = NULL, -0.0 = +0.0, every NaN one value"""
+        h = C.c_void_p()
+        if cols is None:
+            self.check(lib().nqe_distinct_execute(self.handle, table.handle, None, 0, C.byref(h)))
+        else:
+            ks = [int(c) for c in cols]
+            arr = (C.c_int32 * max(1, len(ks)))(*ks)
+            self.check(lib().nqe_distinct_execute(self.handle, table.handle, arr, len(ks), C.byref(h)))
+        return Table(self, h)
+
+    def set_op(self, left: "Table", right: "Table", op) -> "Table":
+        """UNION / INTERSECT / EXCEPT of two tables with the same column types (quirk Q24, `op` a SetOp): every column is a key;
+        INTERSECT and EXCEPT partition distinct(left) in left's order, UNION is distinct(concat(left, right))"""
+        h = C.c_void_p()
+        self.check(lib().nqe_set_op_execute(self.handle, left.handle, right.handle, int(op), C.byref(h)))
         return Table(self, h)
 
     def append_columns(self, table: "Table", extras: Sequence["Table"]) -> "Table":

@@ -983,15 +983,17 @@ std::unique_ptr<nqe_table> probe_duplicates(nqe_ctx *ctx, const nqe_join_table *
 // all of them (`dense` or `slots` is always filled) — that takes none of the fused one-pass tiers: count pass (outer_count_kernel),
 // scan, output-driven write pass (outer_write_kernel), and for the build-preserving side a pass over the build rows
 // (unmatched_build_kernel) + compaction.  The match relation is the inner join's, Q11 included.
-// exact null counts of the nullable columns of `out` (count_set_bits_kernel per column, one read-back for all of them)
-void count_nulls_exact(nqe_ctx *ctx, nqe_table *out, const char *label = "join_outer_null_count") {
+// exact null counts of the nullable columns of `out` (count_set_bits_kernel per column, one read-back for all of them); declared in
+// nqe_internal.hpp (set_ops.hip calls it too): true when it waited for the stream
+} // namespace
+bool count_nulls_exact(nqe_ctx *ctx, nqe_table *out, const char *label) {
     std::vector<size_t> which;
     for (size_t c = 0; c < out->cols.size(); ++c)
         if (out->cols[c].validity && out->cols[c].null_count < 0) which.push_back(c);
-    if (which.empty()) return;
+    if (which.empty()) return false;
     if (out->rows == 0) {
         for (size_t c : which) out->cols[c].null_count = 0;
-        return;
+        return false;
     }
     BufRef set = dev_alloc_zero(ctx, which.size() * 8);
     for (size_t k = 0; k < which.size(); ++k)
@@ -1001,7 +1003,9 @@ void count_nulls_exact(nqe_ctx *ctx, nqe_table *out, const char *label = "join_o
     NQE_HIP_CHECK(hipMemcpyAsync(h.data(), set->ptr, which.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
     sync(ctx);
     for (size_t k = 0; k < which.size(); ++k) out->cols[which[k]].null_count = out->rows - int64_t(h[k]);
+    return true;
 }
+namespace {
 // pass 2 of the outer probe and what follows it (cf. write_duplicate_matches): a left column gets a validity buffer when its source
 // has one or the batch holds a NULL-extended row (`has_null`)
 void write_outer_matches(nqe_ctx *ctx, const nqe_join_table *jt, const nqe_table *right, int64_t M, bool has_null, const BufRef &pmeta, const BufRef &offs, int grid,

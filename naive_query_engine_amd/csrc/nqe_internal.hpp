@@ -344,6 +344,9 @@ bool aggregate_tree_specialised(nqe_ctx *ctx, const nqe_table *in, const nqe_exp
                                 int val_col, int grid, BufRef *partials, uint32_t *span_out, int64_t *bias_out, bool dry_run = false);
 // evaluates `e` over `in` and compacts the result in the same pass
 DevColumn compact_simple_expr(nqe_ctx *ctx, const nqe_table *in, const SimpleExpr &e, const KeepMask &km);
+// hash_join.hip: the exact null_count of every column of `out` that has a validity buffer and a null_count still unknown (< 0) — one
+// counting launch per such column under `label`, one read-back for all of them; true when it waited for the stream
+bool count_nulls_exact(nqe_ctx *ctx, nqe_table *out, const char *label = "join_outer_null_count");
 // aggregate.hip: fails as nqe_aggregate_execute would for this aggregate list (count, function, column index, column type); launches nothing
 void check_aggregates(const nqe_table *in, const nqe_aggregate *aggs, int naggs);
 

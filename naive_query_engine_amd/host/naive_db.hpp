@@ -1197,6 +1197,99 @@ struct PhysicalWindowPlan : PhysicalPlan {
     }
 };
 
+// ---------------------------------------------------------------- DISTINCT and the set operators (no reference file: the planner has no DISTINCT and no set operator)
+// Quirk Q24.  PhysicalDistinctPlan: the rows that are the first occurrence of their tuple over the expressions `on` (nullopt: every
+// column), in input order, with every input column.  PhysicalSetOpPlan: UNION / INTERSECT / EXCEPT, every column a key, left's schema.
+// Like PhysicalSortPlan the input batches are concatenated and ONE batch leaves.  A key that is a bare ColumnExpr is passed by index;
+// any other expression is evaluated into a temporary column that never reaches the output.
+inline std::shared_ptr<nqe_table> concat_batches_shared(const ContextRef &ctx, std::vector<RecordBatch> &batches) {
+    if (batches.size() == 1) return batches[0].shared();
+    std::vector<const nqe_table *> parts;
+    for (auto &b : batches) parts.push_back(b.raw());
+    nqe_table *c = nullptr;
+    ctx->check(nqe_table_concat(ctx->raw(), parts.data(), int32_t(parts.size()), &c));
+    return std::shared_ptr<nqe_table>(c, [](nqe_table *p) { nqe_table_release(p); });
+}
+struct PhysicalDistinctPlan : PhysicalPlan {
+    PhysicalPlanRef input;
+    std::optional<std::vector<PhysicalExprRef>> on;
+    static PhysicalPlanRef create(PhysicalPlanRef input, std::optional<std::vector<PhysicalExprRef>> on = std::nullopt) {
+        auto p = std::make_shared<PhysicalDistinctPlan>();
+        p->input = std::move(input); p->on = std::move(on);
+        return p;
+    }
+    const NaiveSchema &schema() const override { return input->schema(); }
+    std::vector<PhysicalPlanRef> children() const override { return {input}; }
+    std::vector<RecordBatch> execute() override {
+        std::vector<RecordBatch> batches = input->execute();
+        if (batches.empty()) throw ErrorCode(ErrorCode::NotSupported, "distinct over an empty batch list is not supported on the device path");
+        const ContextRef &ctx = batches[0].ctx();
+        const NaiveSchema &s = batches[0].schema();
+        auto release = [](nqe_table *p) { nqe_table_release(p); };
+        std::shared_ptr<nqe_table> in = concat_batches_shared(ctx, batches);
+        nqe_table *out = nullptr;
+        if (!on) {
+            ctx->check(nqe_distinct_execute(ctx->raw(), in.get(), nullptr, 0, &out));
+            return {batches[0].with_table(s, out)};
+        }
+        const int32_t ncols = nqe_table_num_columns(in.get());
+        std::vector<std::shared_ptr<nqe_table>> guards;
+        std::vector<nqe_column> cols(static_cast<size_t>(ncols)); // `in`'s columns, borrowed; the temporaries follow
+        for (int32_t i = 0; i < ncols; ++i) ctx->check(nqe_table_column(in.get(), i, &cols[size_t(i)]));
+        std::vector<int32_t> keys;
+        for (auto &e : *on) {
+            if (const ColumnExpr *c = e->as_column()) {
+                keys.push_back(int32_t(c->resolve(s)));
+                continue;
+            }
+            std::vector<nqe_expr_node> nodes;
+            e->flatten(s, nodes);
+            nqe_table *t = nullptr;
+            ctx->check(nqe_expr_evaluate(ctx->raw(), in.get(), nodes.data(), int32_t(nodes.size()), &t));
+            guards.emplace_back(t, release);
+            nqe_column tc;
+            ctx->check(nqe_table_column(t, 0, &tc));
+            cols.push_back(tc);
+            keys.push_back(int32_t(cols.size()) - 1);
+        }
+        if (cols.size() == size_t(ncols)) {
+            ctx->check(nqe_distinct_execute(ctx->raw(), in.get(), keys.data(), int32_t(keys.size()), &out));
+            return {batches[0].with_table(s, out)};
+        }
+        nqe_table *wide = nullptr;
+        ctx->check(nqe_table_create(ctx->raw(), cols.data(), int32_t(cols.size()), &wide));
+        guards.emplace_back(wide, release);
+        ctx->check(nqe_distinct_execute(ctx->raw(), wide, keys.data(), int32_t(keys.size()), &out));
+        std::shared_ptr<nqe_table> all(out, release);
+        // the input's columns without the temporaries: a view of the result's first columns, which the batch keeps alive
+        std::vector<int32_t> first(static_cast<size_t>(ncols));
+        for (int32_t i = 0; i < ncols; ++i) first[size_t(i)] = i;
+        nqe_table *visible = nullptr;
+        ctx->check(nqe_table_project(ctx->raw(), all.get(), first.data(), ncols, &visible));
+        return {batches[0].with_view(s, visible, {all})};
+    }
+};
+struct PhysicalSetOpPlan : PhysicalPlan {
+    PhysicalPlanRef left, right;
+    nqe_set_op op = NQE_SET_UNION;
+    static PhysicalPlanRef create(PhysicalPlanRef left, PhysicalPlanRef right, nqe_set_op op) {
+        auto p = std::make_shared<PhysicalSetOpPlan>();
+        p->left = std::move(left); p->right = std::move(right); p->op = op;
+        return p;
+    }
+    const NaiveSchema &schema() const override { return left->schema(); }
+    std::vector<PhysicalPlanRef> children() const override { return {left, right}; }
+    std::vector<RecordBatch> execute() override {
+        std::vector<RecordBatch> lb = left->execute(), rb = right->execute();
+        if (lb.empty() || rb.empty()) throw ErrorCode(ErrorCode::NotSupported, "a set operation over an empty batch list is not supported on the device path");
+        const ContextRef &ctx = lb[0].ctx();
+        std::shared_ptr<nqe_table> l = concat_batches_shared(ctx, lb), r = concat_batches_shared(ctx, rb);
+        nqe_table *out = nullptr;
+        ctx->check(nqe_set_op_execute(ctx->raw(), l.get(), r.get(), int32_t(op), &out));
+        return {lb[0].with_table(lb[0].schema(), out)};
+    }
+};
+
 // ---------------------------------------------------------------- physical_plan/visitor.rs:4-24
 struct PhysicalPlanVisitor { // trait PhysicalPlanVistor
     virtual ~PhysicalPlanVisitor() = default;
@@ -1332,6 +1425,8 @@ inline PhysicalPlanRef rewrite(const PhysicalPlanRef &plan) {
     }
     if (auto srt = std::dynamic_pointer_cast<PhysicalSortPlan>(plan)) return PhysicalSortPlan::create(rewrite(srt->input), srt->sort_exprs, srt->fetch);
     if (auto w = std::dynamic_pointer_cast<PhysicalWindowPlan>(plan)) return PhysicalWindowPlan::create(rewrite(w->input), w->partition_by, w->order_by, w->funcs);
+    if (auto d = std::dynamic_pointer_cast<PhysicalDistinctPlan>(plan)) return PhysicalDistinctPlan::create(rewrite(d->input), d->on);
+    if (auto so = std::dynamic_pointer_cast<PhysicalSetOpPlan>(plan)) return PhysicalSetOpPlan::create(rewrite(so->left), rewrite(so->right), so->op);
     if (auto o = std::dynamic_pointer_cast<PhysicalOffsetPlan>(plan)) return PhysicalOffsetPlan::create(rewrite(o->input), o->n);
     if (auto o = std::dynamic_pointer_cast<HashOuterJoin>(plan)) return HashOuterJoin::create(rewrite(o->left), rewrite(o->right), o->on, o->join_type, o->schema_);
     if (auto m = std::dynamic_pointer_cast<MultiKeyHashJoin>(plan)) return MultiKeyHashJoin::create(rewrite(m->left), rewrite(m->right), m->on, m->join_type, m->schema_);

@@ -21,7 +21,7 @@ from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple
 
 from . import capi
-from .arrow_host import AggregateFunc, Column, DType, ErrorCode, Field, RecordBatch, Status, WindowFrame, WindowFunc
+from .arrow_host import AggregateFunc, Column, DType, ErrorCode, Field, RecordBatch, SetOp, Status, WindowFrame, WindowFunc
 from .expression import ColumnExpr, PhysicalExpr
 
 NaiveSchema = List[Field]  # src/logical_plan/schema.rs (qualifiers are ignored at physical planning, Q12)
@@ -874,3 +874,74 @@ class PhysicalWindowPlan(PhysicalPlan):
         out = ctx.window(ctx.append_columns(table, temps) if temps else table, parts, keys, specs)
         out_fields = list(fields) + [f.data_field(fields) for f in self.funcs]
         return [DeviceRecordBatch(out_fields, ctx.append_columns(table, [ctx.project(out, [i]) for i in range(len(self.funcs))]))]
+
+
+# ----------------------------------------------------------------------------- DISTINCT and the set operators
+def _one_table(ctx, batches):
+    return batches[0].table if len(batches) == 1 else ctx.concat([b.table for b in batches])
+
+
+class PhysicalDistinctPlan(PhysicalPlan):
+    """SELECT DISTINCT (quirk Q24; the reference's planner has no DISTINCT): the rows that are the first occurrence of their tuple
+    over the expressions `on` (None: every column), in input order, with every input column.  Like PhysicalSortPlan the input batches
+    are concatenated and ONE batch leaves.  A key that is a bare ColumnExpr is passed by index; any other expression is evaluated into
+    a temporary column that never reaches the output."""
+
+    def __init__(self, input: PhysicalPlan, on: Optional[Sequence[PhysicalExpr]] = None):
+        self.input, self.on = input, None if on is None else list(on)
+
+    @staticmethod
+    def create(input: PhysicalPlan, on: Optional[Sequence[PhysicalExpr]] = None) -> "PhysicalDistinctPlan":
+        return PhysicalDistinctPlan(input, on)
+
+    def schema(self):
+        return self.input.schema()
+
+    def children(self):
+        return [self.input]
+
+    def execute(self):
+        batches = self.input.execute()
+        if not batches:
+            raise ErrorCode(Status.NotSupported, "distinct over an empty batch list is not supported on the device path")
+        ctx = _ctx_of(batches)
+        fields = batches[0].fields
+        table = _one_table(ctx, batches)
+        if self.on is None:
+            return [DeviceRecordBatch(fields, ctx.distinct(table))]
+        temps, cols = [], []
+        for expr in self.on:
+            if isinstance(expr, ColumnExpr):
+                cols.append(expr.resolve(fields))
+            else:
+                temps.append(ctx.expr_evaluate(table, expr.flatten(fields)))
+                cols.append(len(fields) + len(temps) - 1)
+        if not temps:
+            return [DeviceRecordBatch(fields, ctx.distinct(table, cols))]
+        out = ctx.distinct(ctx.append_columns(table, temps), cols)
+        return [DeviceRecordBatch(fields, ctx.project(out, list(range(len(fields)))))]
+
+
+class PhysicalSetOpPlan(PhysicalPlan):
+    """UNION / INTERSECT / EXCEPT (quirk Q24; the reference's planner has no set operator): every column is a key, both inputs need the
+    same column types.  The batches of each side are concatenated and ONE batch leaves, with left's schema."""
+
+    def __init__(self, left: PhysicalPlan, right: PhysicalPlan, op: SetOp):
+        self.left, self.right, self.op = left, right, SetOp(op)
+
+    @staticmethod
+    def create(left: PhysicalPlan, right: PhysicalPlan, op: SetOp) -> "PhysicalSetOpPlan":
+        return PhysicalSetOpPlan(left, right, op)
+
+    def schema(self):
+        return self.left.schema()
+
+    def children(self):
+        return [self.left, self.right]
+
+    def execute(self):
+        lb, rb = self.left.execute(), self.right.execute()
+        if not lb or not rb:
+            raise ErrorCode(Status.NotSupported, "a set operation over an empty batch list is not supported on the device path")
+        ctx = _ctx_of(lb)
+        return [DeviceRecordBatch(lb[0].fields, ctx.set_op(_one_table(ctx, lb), _one_table(ctx, rb), self.op))]

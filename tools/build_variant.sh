@@ -12,7 +12,7 @@ D=_var_$NAME
 mkdir -p $D
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 CXX="-O3 -std=c++17 -fPIC --offload-arch=gfx950 --offload-compress -munsafe-fp-atomics -Wall -Wno-unused-function -fno-gpu-rdc $FLAGS"
-UNITS="context exchange arrow_c expr selection sort aggregate aggregate_tail aggregate_fast aggregate_partition aggregate_tiny hash_join strings csv cross_join nested_loop_join order_by group_keys join_keys window"
+UNITS="context exchange arrow_c expr selection sort aggregate aggregate_tail aggregate_fast aggregate_partition aggregate_tiny hash_join strings csv cross_join nested_loop_join order_by group_keys join_keys window set_ops"
 pids=()
 if [ -n "$NQE_VARIANT_UNITS" ]; then
   for f in $UNITS; do cp $f.o $D/$f.o; done
