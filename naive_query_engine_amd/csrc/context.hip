@@ -928,7 +928,8 @@ nqe_status nqe_table_project(nqe_ctx *ctx, const nqe_table *in, const int32_t *i
 nqe_status nqe_table_slice(nqe_ctx *ctx, const nqe_table *in, int64_t offset, int64_t length, nqe_table **out) {
     NQE_API_BEGIN(ctx)
     if (!in || !out) fail(NQE_ERR_INVALID_ARGUMENT, "bad arguments");
-    if (offset < 0 || length < 0 || offset + length > in->rows) fail(NQE_ERR_ARROW, "slice out of bounds");
+    // compared without adding: offset + length wraps for a pair like (2^62, 2^62) and would pass as a negative sum
+    if (offset < 0 || length < 0 || offset > in->rows || length > in->rows - offset) fail(NQE_ERR_ARROW, "slice out of bounds");
     auto t = std::make_unique<nqe_table>();
     t->ctx = ctx;
     t->rows = length;
@@ -982,6 +983,7 @@ nqe_status nqe_table_pack_words(nqe_ctx *ctx, const nqe_table *const *tables, in
         }
     }
     if (rows > stride_rows) fail(NQE_ERR_INVALID_ARGUMENT, "pack: rows exceed the stride");
+    // rows * ncols cannot wrap: rows is the row count of real 8-byte columns and ncols <= PACK_MAX_COLS; the caller's dst holds ncols * stride + 1 words
     pa.rows = rows;
     pa.stride = stride_rows;
     launch(ctx, "pack_words", pack_words_kernel, dim3(unsigned(std::max<int64_t>(1, std::min<int64_t>(1024, (rows * pa.ncols + 255) / 256)))), dim3(256), 0, pa,
@@ -1002,6 +1004,8 @@ nqe_status nqe_table_unpack_words(nqe_ctx *ctx, const void *src_device, int32_t 
         ua.offset[p] = total;
         total += counts[p];
     }
+    // total * num_columns * 8 cannot wrap: total <= num_parts * stride_rows, and the caller's src really holds
+    // num_parts * (num_columns * stride_rows + 1) words
     ua.offset[num_parts] = total;
     ua.nparts = num_parts;
     ua.ncols = num_columns;
