@@ -15,6 +15,10 @@
 //      empty numeric fields are NULL; a scan of the lengths gives the Utf8 offsets and a second walk copies the bytes
 //      (with "" unescaped).
 // Schema inference touches max_read_records records only and runs on the host (it decides the kernels' column types).
+//
+// Edges the tests pin (tests/csv_util.py: CHUNK, BLOCK, WG_BYTES, CARRY_BYTES, FIELD_BLOCK move with the constants below):
+// 64 bytes (CSV_CHUNK, one thread), 16 384 (x CSV_BLOCK, one workgroup scan), 4 194 304 (x CSV_BLOCK again, one tile of the
+// totals loop, where the carry starts to matter) and 256 rows (one workgroup of csv_fields_kernel).
 #include <algorithm>
 #include <cstring>
 #include <memory>
@@ -22,6 +26,7 @@
 #include <vector>
 
 #include "csv_parse.hpp"
+#include "csv_split.hpp"
 #include "device_utils.hpp"
 #include "nqe_internal.hpp"
 
@@ -32,33 +37,8 @@ constexpr int CSV_CHUNK = 64;   // bytes per thread in the splitting passes
 constexpr int CSV_BLOCK = 256;
 constexpr int CSV_MAX_COLS = 64;
 
-// quoting automaton of one record stream
-enum : uint32_t { ST_R = 0 /* record start */, ST_F = 1 /* field start */, ST_U = 2 /* unquoted */, ST_Q = 3 /* quoted */, ST_E = 4 /* quote in quoted */ };
-constexpr uint32_t VEC_ID = ST_R | (ST_F << 3) | (ST_U << 6) | (ST_Q << 9) | (ST_E << 12);
-
-__host__ __device__ inline bool is_nl(uint8_t c) { return c == '\n' || c == '\r'; }
-
-// next state; *rec_start: this byte opens a record; *rec_end: this byte (a terminator) closes one
-__host__ __device__ inline uint32_t csv_step(uint32_t st, uint8_t c, uint8_t delim, bool *rec_start, bool *rec_end) {
-    const bool nl = is_nl(c);
-    *rec_start = st == ST_R && !nl;
-    *rec_end = nl && (st == ST_F || st == ST_U || st == ST_E);
-    switch (st) {
-    case ST_R:
-    case ST_F: return nl ? ST_R : c == '"' ? ST_Q : c == delim ? ST_F : ST_U;
-    case ST_U: return nl ? ST_R : c == delim ? ST_F : ST_U;
-    case ST_Q: return c == '"' ? ST_E : ST_Q;
-    default: return c == '"' ? ST_Q : nl ? ST_R : c == delim ? ST_F : ST_U; // ST_E
-    }
-}
-__host__ __device__ inline uint32_t vec_get(uint32_t v, uint32_t s) { return (v >> (3 * s)) & 7u; }
-// (a then b)
-__host__ __device__ inline uint32_t vec_compose(uint32_t a, uint32_t b) {
-    uint32_t c = 0;
-#pragma unroll
-    for (uint32_t s = 0; s < 5; ++s) c |= vec_get(b, vec_get(a, s)) << (3 * s);
-    return c;
-}
+// the quoting automaton (ST_*, csv_step) and its transition vectors (VEC_ID, vec_get, vec_compose): csv_split.hpp
+using namespace csv_split;
 
 // workgroup inclusive scan of transition vectors (Hillis-Steele in LDS); returns the exclusive prefix of the thread
 __device__ inline uint32_t block_scan_vec(uint32_t v, uint32_t *lds, uint32_t *total) {
@@ -154,6 +134,7 @@ struct CsvCols {
 enum { CSV_FLAG_FIELDS = 0, CSV_FLAG_PARSE = 1, CSV_FLAG_NULLS = 2 /* + column */ };
 
 // One thread per record.  PASS 0: split + convert (+ Utf8 lengths); PASS 1: copy Utf8 bytes to their offsets.
+// bad_row[f]: the first row that raised flag f (f = CSV_FLAG_FIELDS, CSV_FLAG_PARSE), one cell per message the host prints.
 template <int PASS>
 __global__ void __launch_bounds__(256) csv_fields_kernel(const uint8_t *bytes, const int64_t *rec_start, const int64_t *rec_end, int64_t first_rec, int64_t rows,
                                                          uint8_t delim, CsvCols cc, int *flags, int64_t *bad_row) {
@@ -209,7 +190,7 @@ __global__ void __launch_bounds__(256) csv_fields_kernel(const uint8_t *bytes, c
                     else { bool v; ok = csvp::parse_bool(p, len, &v); w = v ? 1 : 0; }
                     if (!ok) {
                         atomicOr(&flags[CSV_FLAG_PARSE], 1);
-                        atomicMin((unsigned long long *)bad_row, (unsigned long long)r);
+                        atomicMin((unsigned long long *)&bad_row[CSV_FLAG_PARSE], (unsigned long long)r);
                     }
                 } else atomicOr(&flags[CSV_FLAG_NULLS + col], 1);
                 if (dt == NQE_BOOLEAN) cc.bool_bytes[col][r] = uint8_t(w);
@@ -224,7 +205,7 @@ __global__ void __launch_bounds__(256) csv_fields_kernel(const uint8_t *bytes, c
     }
     if (PASS == 0 && col != cc.ncols) {
         atomicOr(&flags[CSV_FLAG_FIELDS], 1);
-        atomicMin((unsigned long long *)bad_row, (unsigned long long)r);
+        atomicMin((unsigned long long *)&bad_row[CSV_FLAG_FIELDS], (unsigned long long)r);
     }
 }
 
@@ -412,8 +393,8 @@ nqe_status nqe_csv_read(nqe_ctx *ctx, const void *bytes, int32_t location, int64
     BufRef slen = dev_alloc_zero(ctx, size_t(std::max(n_utf8, 1)) * size_t(rows + 1) * 4);
     cc.str_len = (uint32_t *)slen->ptr;
     BufRef flags = dev_alloc_zero(ctx, sizeof(int) * (CSV_FLAG_NULLS + CSV_MAX_COLS) + 8);
-    BufRef bad = dev_alloc(ctx, 8);
-    NQE_HIP_CHECK(hipMemsetAsync(bad->ptr, 0xff, 8, ctx->stream));
+    BufRef bad = dev_alloc(ctx, 16); // [CSV_FLAG_FIELDS], [CSV_FLAG_PARSE]
+    NQE_HIP_CHECK(hipMemsetAsync(bad->ptr, 0xff, 16, ctx->stream));
     if (rows) {
         const dim3 grid(unsigned((rows + 255) / 256));
         launch(ctx, "csv_fields", csv_fields_kernel<0>, grid, dim3(256), 0, db, (const int64_t *)rstart->ptr, (const int64_t *)rend->ptr, first, rows, delim, cc,
@@ -421,9 +402,12 @@ nqe_status nqe_csv_read(nqe_ctx *ctx, const void *bytes, int32_t location, int64
     }
     std::vector<int> hf(static_cast<size_t>(CSV_FLAG_NULLS + CSV_MAX_COLS), 0);
     NQE_HIP_CHECK(hipMemcpyAsync(hf.data(), flags->ptr, hf.size() * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    const int64_t bad_row = int64_t(read_scalar(ctx, (const uint64_t *)bad->ptr));
-    if (hf[CSV_FLAG_FIELDS]) fail(NQE_ERR_ARROW, "csv: record " + std::to_string(bad_row + first + 1) + " has a different number of fields than the schema");
-    if (hf[CSV_FLAG_PARSE]) fail(NQE_ERR_ARROW, "csv: error while parsing a value at line " + std::to_string(bad_row + first + 1));
+    int64_t bad_row[2];
+    NQE_HIP_CHECK(hipMemcpyAsync(bad_row, bad->ptr, 16, hipMemcpyDeviceToHost, ctx->stream));
+    sync(ctx);
+    if (hf[CSV_FLAG_FIELDS])
+        fail(NQE_ERR_ARROW, "csv: record " + std::to_string(bad_row[CSV_FLAG_FIELDS] + first + 1) + " has a different number of fields than the schema");
+    if (hf[CSV_FLAG_PARSE]) fail(NQE_ERR_ARROW, "csv: error while parsing a value at line " + std::to_string(bad_row[CSV_FLAG_PARSE] + first + 1));
     for (int c = 0; c < num_columns; ++c) {
         DevColumn &d = t->cols[size_t(c)];
         if (dtypes[c] == NQE_UTF8) {

@@ -1,5 +1,5 @@
 """CPU: the CSV number parser (csrc/csv_parse.hpp, the code the device kernel runs) against glibc strtod/strtoll on
-1.4 M random, halfway and edge-case strings; the oracle's sequential CSV reader against the reference's fixtures."""
+1.4 M random, halfway and edge-case strings; the record splitter's transition vectors (csrc/csv_split.hpp); the oracle's sequential CSV reader against the reference's fixtures."""
 import os
 import subprocess
 
@@ -11,6 +11,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_number_parser_matches_strtod_on_host():
     exe = os.path.join(ROOT, "tests", "cpp", "test_csv_parse")
     subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", os.path.join(ROOT, "tests", "cpp", "test_csv_parse.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout[-2000:]
+    assert " 0 failures" in out.stdout
+
+
+def test_record_splitter_vectors_compose_like_the_sequential_walk_on_host():
+    """csrc/csv_split.hpp (the automaton and transition vectors csv.hip's kernels run), exhaustively over the four byte
+    classes: composition, associativity, identity, every chunking of every string of <= 8 bytes, equal start/end counts"""
+    exe = os.path.join(ROOT, "tests", "cpp", "test_csv_split")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", os.path.join(ROOT, "tests", "cpp", "test_csv_split.cpp"), "-o", exe])
     out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stdout[-2000:]
     assert " 0 failures" in out.stdout
