@@ -794,6 +794,88 @@ nqe_status nqe_window_execute(nqe_ctx *ctx, const nqe_table *in, const int32_t *
                               const nqe_sort_key *order_keys, int32_t num_order, const nqe_window_spec *funcs,
                               int32_t num_funcs, nqe_table **out);
 
+/* ------------------------------------------------------------------ window functions, the wider entry
+ * nqe_window_execute_ex is a superset of nqe_window_execute (quirk Q23): the same window — sorted
+ * order, partitions, peers, ties, word for word — and the same output shape (ONE table of num_funcs
+ * columns and in->rows rows IN INPUT ORDER, nothing kept between calls), with four more functions
+ * and one more frame.  Below, i is a row's position in the sorted order and pf / pl the first and
+ * last position of its partition.
+ *   functions 0..7 over frames 0..2   exactly nqe_window_execute: bit-identical results
+ *   NQE_FRAMEX_ROWS_BETWEEN   (aggregates, FIRST_VALUE, LAST_VALUE) the positions
+ *                 [max(i + start, pf), min(i + end, pl)]: start = -3 is 3 PRECEDING, 0 CURRENT ROW,
+ *                 2 is 2 FOLLOWING; NQE_FRAME_UNBOUNDED_PRECEDING only as start,
+ *                 NQE_FRAME_UNBOUNDED_FOLLOWING only as end.  A frame may exclude the current row
+ *                 (-3 .. -1, 1 .. 3) and may be EMPTY; an empty frame gives Q10's start values as a
+ *                 frame of NULLs does: count 0, sum 0.0, avg NaN, min f64::MAX, max f64::MIN.  The
+ *                 aggregates keep Q10 in every respect (f64 conversion, NULL skipped, min ignores
+ *                 NaN, max becomes NaN, avg divides by the count as u32); UInt64 / Float64 without
+ *                 validity.  No value outside a frame takes part in its result: a bounded frame is
+ *                 combined from at most two segmented scans, never from a difference of prefixes.
+ *   LAG / LEAD    (column, param = k >= 0) the value of the row at position i - k / i + k when that
+ *                 lies in [pf, pl], else default_value when has_default, else NULL.  The column's
+ *                 dtype; the 8 bytes are copied, not converted.  A NULL source row gives NULL; k = 0
+ *                 is the row itself.  frame, start and end are ignored.
+ *   FIRST_VALUE / LAST_VALUE   (column, frame) the value, with its validity, at the frame's first /
+ *                 last position, for any of the four frames (ROWS: [pf, i]; RANGE: [pf, the last
+ *                 peer]; PARTITION: [pf, pl]); an empty frame gives NULL.
+ *   NTILE         (param = b >= 1) UInt64, 1-based: with m = pl - pf + 1, q = m / b, r = m % b the
+ *                 first r buckets hold q + 1 rows, the others q (SQL's rule).  column and frame are
+ *                 ignored.
+ * The columns of LAG / LEAD / FIRST_VALUE / LAST_VALUE (Int64 / UInt64 / Float64 arguments only)
+ * report an exact null_count; their validity buffer is absent when it is 0.
+ * Errors, all before any launch or allocation, in this order: (1) NULL ctx / in / out or a NULL
+ * array with a positive count NQE_ERR_INVALID_ARGUMENT; (2) per function in list order, each
+ * NQE_ERR_INVALID_ARGUMENT: func outside the enum; for a framed function (aggregates, FIRST_VALUE,
+ * LAST_VALUE) frame outside the enum; ROWS_BETWEEN with start == UNBOUNDED_FOLLOWING, end ==
+ * UNBOUNDED_PRECEDING or start > end; LAG / LEAD with param < 0; NTILE with param < 1;
+ * (3) num_funcs <= 0 NQE_ERR_PLAN; (4) more keys or functions than NQE_MAX_WINDOW_KEYS /
+ * NQE_MAX_WINDOW_FUNCS NQE_ERR_NOT_SUPPORTED; (5) a key or value column index out of range
+ * NQE_ERR_NOT_SUPPORTED; (6) a key dtype the sort refuses, an aggregate over Boolean / Utf8, a
+ * value function over anything but Int64 / UInt64 / Float64 NQE_ERR_NOT_SUPPORTED; (7) 2^32 rows
+ * or more NQE_ERR_NOT_SUPPORTED.  Zero rows give a 0-row table with every column.
+ * Out of scope: RANGE and GROUPS frames with offsets; EXCLUDE; IGNORE NULLS; NTH_VALUE /
+ * PERCENT_RANK / CUME_DIST; value functions over Boolean / Utf8; several different windows in one
+ * call (call once per window); SQL parsing. */
+typedef enum nqe_window_func_ex { /* 0..7: the values of nqe_window_func, same meaning */
+    NQE_WINX_ROW_NUMBER = 0,
+    NQE_WINX_RANK = 1,
+    NQE_WINX_DENSE_RANK = 2,
+    NQE_WINX_COUNT = 3,
+    NQE_WINX_SUM = 4,
+    NQE_WINX_MIN = 5,
+    NQE_WINX_MAX = 6,
+    NQE_WINX_AVG = 7,
+    NQE_WINX_LAG = 8,
+    NQE_WINX_LEAD = 9,
+    NQE_WINX_FIRST_VALUE = 10,
+    NQE_WINX_LAST_VALUE = 11,
+    NQE_WINX_NTILE = 12
+} nqe_window_func_ex;
+typedef enum nqe_window_frame_ex { /* 0..2: the values of nqe_window_frame */
+    NQE_FRAMEX_PARTITION = 0,
+    NQE_FRAMEX_ROWS = 1,
+    NQE_FRAMEX_RANGE = 2,
+    NQE_FRAMEX_ROWS_BETWEEN = 3 /* ROWS BETWEEN start AND end, both offsets from the current row */
+} nqe_window_frame_ex;
+#define NQE_FRAME_UNBOUNDED_PRECEDING INT64_MIN
+#define NQE_FRAME_UNBOUNDED_FOLLOWING INT64_MAX
+typedef struct nqe_window_spec_ex {
+    int32_t func;        /* nqe_window_func_ex */
+    int32_t column;      /* the argument's column; ignored by the ranking functions and NTILE */
+    int32_t frame;       /* nqe_window_frame_ex; read by the aggregates, FIRST_VALUE and LAST_VALUE */
+    int32_t has_default; /* LAG / LEAD: default_value stands in for a row outside the partition */
+    int64_t start, end;  /* ROWS_BETWEEN only: signed offsets from the current row */
+    int64_t param;       /* LAG / LEAD: rows back / ahead, >= 0; NTILE: buckets, >= 1 */
+    union {
+        int64_t i64;
+        uint64_t u64;
+        double f64;
+    } default_value;     /* 8 bytes of the column's dtype */
+} nqe_window_spec_ex;    /* sizeof == 48 */
+nqe_status nqe_window_execute_ex(nqe_ctx *ctx, const nqe_table *in, const int32_t *partition_cols, int32_t num_partition,
+                                 const nqe_sort_key *order_keys, int32_t num_order, const nqe_window_spec_ex *funcs,
+                                 int32_t num_funcs, nqe_table **out);
+
 /* ------------------------------------------------------------------ DISTINCT and the set operators
  * SELECT DISTINCT, UNION, INTERSECT and EXCEPT — quirk Q24: the reference has none of them (its
  * JoinType is {Inner, Left, Right, Cross} and its SQL planner knows no DISTINCT and no set

@@ -79,6 +79,14 @@ pub struct NqeWindowSpec { pub func: i32, pub column: i32, pub frame: i32 }
 pub const NQE_WIN_ROW_NUMBER: i32 = 0; pub const NQE_WIN_RANK: i32 = 1; pub const NQE_WIN_DENSE_RANK: i32 = 2; pub const NQE_WIN_COUNT: i32 = 3;
 pub const NQE_WIN_SUM: i32 = 4; pub const NQE_WIN_MIN: i32 = 5; pub const NQE_WIN_MAX: i32 = 6; pub const NQE_WIN_AVG: i32 = 7;
 pub const NQE_FRAME_PARTITION: i32 = 0; pub const NQE_FRAME_ROWS: i32 = 1; pub const NQE_FRAME_RANGE: i32 = 2;
+/// nqe_window_spec_ex: one function of nqe_window_execute_ex (48 bytes).  `start` / `end` are read with frame NQE_FRAMEX_ROWS_BETWEEN only
+/// (i64::MIN / i64::MAX: unbounded), `param` is k of LAG / LEAD and the bucket count of NTILE, `default_value` 8 bytes of the column's dtype
+#[repr(C)] #[derive(Clone, Copy, Debug)]
+pub struct NqeWindowSpecEx { pub func: i32, pub column: i32, pub frame: i32, pub has_default: i32, pub start: i64, pub end: i64, pub param: i64, pub default_value: u64 }
+// nqe_window_func_ex / nqe_window_frame_ex: 0..7 and 0..2 are the values above
+pub const NQE_WINX_LAG: i32 = 8; pub const NQE_WINX_LEAD: i32 = 9; pub const NQE_WINX_FIRST_VALUE: i32 = 10; pub const NQE_WINX_LAST_VALUE: i32 = 11;
+pub const NQE_WINX_NTILE: i32 = 12; pub const NQE_FRAMEX_ROWS_BETWEEN: i32 = 3;
+pub const NQE_FRAME_UNBOUNDED_PRECEDING: i64 = i64::MIN; pub const NQE_FRAME_UNBOUNDED_FOLLOWING: i64 = i64::MAX;
 // nqe_set_op (quirk Q24)
 pub const NQE_SET_UNION: i32 = 0; pub const NQE_SET_INTERSECT: i32 = 1; pub const NQE_SET_EXCEPT: i32 = 2;
 pub enum NqeCtx {}
@@ -141,6 +149,8 @@ extern "C" {
     fn nqe_sort_execute(ctx: *mut NqeCtx, input: *const NqeTable, keys: *const NqeSortKey, num_keys: i32, fetch: i64, out: *mut *mut NqeTable) -> i32;
     fn nqe_window_execute(ctx: *mut NqeCtx, input: *const NqeTable, partition_cols: *const i32, num_partition: i32, order_keys: *const NqeSortKey, num_order: i32,
                           funcs: *const NqeWindowSpec, num_funcs: i32, out: *mut *mut NqeTable) -> i32;
+    fn nqe_window_execute_ex(ctx: *mut NqeCtx, input: *const NqeTable, partition_cols: *const i32, num_partition: i32, order_keys: *const NqeSortKey, num_order: i32,
+                             funcs: *const NqeWindowSpecEx, num_funcs: i32, out: *mut *mut NqeTable) -> i32;
     fn nqe_distinct_execute(ctx: *mut NqeCtx, input: *const NqeTable, cols: *const i32, num_cols: i32, out: *mut *mut NqeTable) -> i32;
     fn nqe_set_op_execute(ctx: *mut NqeCtx, left: *const NqeTable, right: *const NqeTable, op: i32, out: *mut *mut NqeTable) -> i32;
 }
@@ -1019,6 +1029,56 @@ impl PhysicalPlan for GpuWindowPlan {
     fn as_gpu(&self) -> Option<&dyn GpuExec> { Some(self) }
 }
 
+/// GpuWindowPlan over nqe_window_execute_ex: the same window and the same shape, with LAG / LEAD / FIRST_VALUE / LAST_VALUE / NTILE and ROWS
+/// BETWEEN frames (NqeWindowSpecEx).  The value functions' fields are nullable and have their argument column's type; NTILE is UInt64.
+#[derive(Debug)]
+pub struct GpuWindowPlanEx {
+    input: PhysicalPlanRef, partition_by: Vec<i32>, order_by: Vec<NqeSortKey>, funcs: Vec<NqeWindowSpecEx>, names: Vec<String>, out_schema: NaiveSchema, ctx: Arc<GpuCtx>,
+}
+impl GpuWindowPlanEx {
+    pub fn create(ctx: Arc<GpuCtx>, input: PhysicalPlanRef, partition_by: Vec<i32>, order_by: Vec<NqeSortKey>, funcs: Vec<NqeWindowSpecEx>, names: Vec<String>) -> PhysicalPlanRef {
+        let mut fields: Vec<NaiveField> = input.schema().fields().clone();
+        for (f, name) in funcs.iter().zip(names.iter()) {
+            let value = f.func >= NQE_WINX_LAG && f.func <= NQE_WINX_LAST_VALUE;
+            let dt = if value { input.schema().fields()[f.column as usize].data_type().clone() }
+                     else if f.func <= NQE_WIN_COUNT || f.func == NQE_WINX_NTILE { DataType::UInt64 } else { DataType::Float64 };
+            fields.push(NaiveField::new(None, name.as_str(), dt, value));
+        }
+        Arc::new(Self { input, partition_by, order_by, funcs, names, out_schema: NaiveSchema::new(fields), ctx })
+    }
+}
+impl GpuExec for GpuWindowPlanEx {
+    fn execute_device(&self) -> Result<Vec<GpuBatch>> {
+        let batches = child_device(&self.ctx, &self.input)?;
+        if batches.is_empty() { return Err(ErrorCode::NotSupported("window functions over an empty batch list are not supported on the device path".to_string())); }
+        let all = self.ctx.concat(&batches)?;
+        let mut w = std::ptr::null_mut();
+        self.ctx.check(unsafe { nqe_window_execute_ex(self.ctx.0, all.table.0, self.partition_by.as_ptr(), self.partition_by.len() as i32, self.order_by.as_ptr(),
+                                                      self.order_by.len() as i32, self.funcs.as_ptr(), self.funcs.len() as i32, &mut w) })?;
+        let win = GpuBatch::wrap(w);
+        // as in GpuWindowPlan: a view over both tables, copied into a table of its own before they go away
+        let mut cols: Vec<NqeColumn> = vec![];
+        for t in [&all.table, &win.table] {
+            for i in 0..t.num_columns() as i32 {
+                let mut info: NqeColumn = unsafe { std::mem::zeroed() };
+                self.ctx.check(unsafe { nqe_table_column(t.0, i, &mut info) })?;
+                cols.push(info);
+            }
+        }
+        let mut both = std::ptr::null_mut();
+        self.ctx.check(unsafe { nqe_table_create(self.ctx.0, cols.as_ptr(), cols.len() as i32, &mut both) })?;
+        let view = GpuBatch::wrap(both);
+        Ok(vec![self.ctx.slice(&view, 0, view.num_rows())?])
+    }
+}
+impl PhysicalPlan for GpuWindowPlanEx {
+    fn schema(&self) -> &NaiveSchema { &self.out_schema }
+    fn children(&self) -> Result<Vec<PhysicalPlanRef>> { Ok(vec![self.input.clone()]) }
+    fn execute(&self) -> Result<Vec<RecordBatch>> { self.ctx.download_all(&self.execute_device()?, &self.out_schema) }
+    fn as_any(&self) -> &dyn Any { self }
+    fn as_gpu(&self) -> Option<&dyn GpuExec> { Some(self) }
+}
+
 /// SELECT DISTINCT (quirk Q24: the reference's planner has no DISTINCT): the input batches are concatenated and ONE batch with the input's
 /// schema leaves — the rows that are the first occurrence of their tuple over the key columns `cols` (None: every column), in input
 /// order.  NULL = NULL, -0.0 = +0.0, every NaN one value.  A front end that plans DISTINCT creates it directly.
@@ -1187,6 +1247,9 @@ pub fn rewrite_sharded(ctx: &Arc<GpuCtx>, comm: Option<&Arc<GpuComm>>, plan: Phy
     }
     if let Some(w) = any.downcast_ref::<GpuWindowPlan>() { // keeps its operator, with a rewritten child (a limit above it stays a limit)
         return Ok(GpuWindowPlan::create(ctx.clone(), rewrite(ctx, w.input.clone())?, w.partition_by.clone(), w.order_by.clone(), w.funcs.clone(), w.names.clone()));
+    }
+    if let Some(w) = any.downcast_ref::<GpuWindowPlanEx>() { // the same for the wider entry
+        return Ok(GpuWindowPlanEx::create(ctx.clone(), rewrite(ctx, w.input.clone())?, w.partition_by.clone(), w.order_by.clone(), w.funcs.clone(), w.names.clone()));
     }
     if let Some(d) = any.downcast_ref::<GpuDistinctPlan>() { // quirk Q24: the node stays, its child is rewritten
         return Ok(GpuDistinctPlan::create(ctx.clone(), rewrite(ctx, d.input.clone())?, d.cols.clone()));

@@ -13,13 +13,13 @@ Layout:
   parallel.py      row-range sharding across GPUs: thin caller of the C ABI's sharded entry points (RCCL)
 """
 from .arrow_host import (AggregateFunc, Column, DType, ErrorCode, Field, Operator, RecordBatch, ScalarValue, SetOp, Status,
-                         UnaryOperator, WindowFrame, WindowFunc, read_csv)
+                         UnaryOperator, WindowFrame, WindowFrameEx, WindowFunc, WindowFuncEx, read_csv)
 from .expression import ColumnExpr, PhysicalBinaryExpr, PhysicalExpr, PhysicalLiteralExpr, PhysicalUnaryExpr
 
 __all__ = [
     "AggregateFunc", "Column", "DType", "ErrorCode", "Field", "Operator", "RecordBatch", "ScalarValue", "Status",
     "read_csv", "ColumnExpr", "PhysicalBinaryExpr", "PhysicalExpr", "PhysicalLiteralExpr", "PhysicalUnaryExpr", "UnaryOperator",
-    "WindowFrame", "WindowFunc", "SetOp",
+    "WindowFrame", "WindowFunc", "SetOp", "WindowFrameEx", "WindowFuncEx",
 ]
 
 

@@ -96,6 +96,33 @@ class WindowFrame(enum.IntEnum):
     Range = 2
 
 
+class WindowFuncEx(enum.IntEnum):
+    """nqe_window_func_ex (nqe_window_execute_ex): WindowFunc's eight with the same values, then the value functions and NTILE"""
+
+    RowNumber = 0
+    Rank = 1
+    DenseRank = 2
+    Count = 3
+    Sum = 4
+    Min = 5
+    Max = 6
+    Avg = 7
+    Lag = 8
+    Lead = 9
+    FirstValue = 10
+    LastValue = 11
+    Ntile = 12
+
+
+class WindowFrameEx(enum.IntEnum):
+    """nqe_window_frame_ex: WindowFrame's three with the same values, and ROWS BETWEEN start AND end (signed offsets from the current row)"""
+
+    Partition = 0
+    Rows = 1
+    Range = 2
+    RowsBetween = 3
+
+
 class SetOp(enum.IntEnum):
     """nqe_set_op (include/nqe.h; quirk Q24: the reference has no set operator)"""
 

@@ -29,7 +29,7 @@ SYMBOLS = [
     "nqe_filter", "nqe_selection_execute", "nqe_projection_execute", "nqe_selection_projection_execute",
     "nqe_aggregate_execute", "nqe_aggregate_partial", "nqe_aggregate_merge", "nqe_aggregate_merge_packed", "nqe_group_aggregate_execute", "nqe_hash_join_execute",
     "nqe_hash_join_build", "nqe_hash_join_probe", "nqe_join_table_release", "nqe_join_marks_create", "nqe_join_marks_release",
-    "nqe_hash_join_probe_outer", "nqe_hash_join_unmatched_build", "nqe_hash_join_build_keys", "nqe_hash_join_probe_keys", "nqe_hash_join_execute_keys", "nqe_hash_join_probe_semi", "nqe_hash_join_marked_build", "nqe_cross_join_execute", "nqe_nested_loop_join_execute", "nqe_sort_execute", "nqe_window_execute", "nqe_distinct_execute", "nqe_set_op_execute", "nqe_take", "nqe_synth_fill",
+    "nqe_hash_join_probe_outer", "nqe_hash_join_unmatched_build", "nqe_hash_join_build_keys", "nqe_hash_join_probe_keys", "nqe_hash_join_execute_keys", "nqe_hash_join_probe_semi", "nqe_hash_join_marked_build", "nqe_cross_join_execute", "nqe_nested_loop_join_execute", "nqe_sort_execute", "nqe_window_execute", "nqe_window_execute_ex", "nqe_distinct_execute", "nqe_set_op_execute", "nqe_take", "nqe_synth_fill",
     "nqe_device_alloc", "nqe_device_free",
     "nqe_comm_get_unique_id", "nqe_comm_rccl_version", "nqe_comm_create", "nqe_comm_create_custom", "nqe_comm_create_p2p", "nqe_comm_destroy", "nqe_comm_rank",
     "nqe_comm_world", "nqe_table_all_gather", "nqe_sharded_aggregate_execute", "nqe_sharded_hash_join_probe",
@@ -67,6 +67,22 @@ class NqeWindowSpec(C.Structure):
     """nqe_window_spec (include/nqe.h): one window function; `column` and `frame` are ignored by the three ranking functions"""
     _fields_ = [("func", C.c_int32), ("column", C.c_int32), ("frame", C.c_int32)]
 
+
+class NqeWindowDefault(C.Union):
+    """the default_value of nqe_window_spec_ex: 8 bytes of the argument column's dtype"""
+    _fields_ = [("i64", C.c_int64), ("u64", C.c_uint64), ("f64", C.c_double)]
+
+
+class NqeWindowSpecEx(C.Structure):
+    """nqe_window_spec_ex (include/nqe.h): one function of nqe_window_execute_ex; start / end are read with frame ROWS_BETWEEN only,
+    param is k of LAG / LEAD and the bucket count of NTILE"""
+    _fields_ = [("func", C.c_int32), ("column", C.c_int32), ("frame", C.c_int32), ("has_default", C.c_int32), ("start", C.c_int64), ("end", C.c_int64),
+                ("param", C.c_int64), ("default_value", NqeWindowDefault)]
+
+
+assert C.sizeof(NqeWindowSpecEx) == 48 and [getattr(NqeWindowSpecEx, f).offset for f, _ in NqeWindowSpecEx._fields_] == [0, 4, 8, 12, 16, 24, 32, 40]
+FRAME_UNBOUNDED_PRECEDING = -(2 ** 63)  # NQE_FRAME_UNBOUNDED_PRECEDING
+FRAME_UNBOUNDED_FOLLOWING = 2 ** 63 - 1  # NQE_FRAME_UNBOUNDED_FOLLOWING
 
 _P2P_SEND_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p)
 
@@ -155,6 +171,7 @@ def lib():
         "nqe_nested_loop_join_execute": (i32, [vp, vp, vp, i32, i32, pvp]),
         "nqe_sort_execute": (i32, [vp, vp, C.POINTER(NqeSortKey), i32, i64, pvp]),
         "nqe_window_execute": (i32, [vp, vp, C.POINTER(i32), i32, C.POINTER(NqeSortKey), i32, C.POINTER(NqeWindowSpec), i32, pvp]),
+        "nqe_window_execute_ex": (i32, [vp, vp, C.POINTER(i32), i32, C.POINTER(NqeSortKey), i32, C.POINTER(NqeWindowSpecEx), i32, pvp]),
         "nqe_distinct_execute": (i32, [vp, vp, C.POINTER(i32), i32, pvp]),
         "nqe_set_op_execute": (i32, [vp, vp, vp, i32, pvp]),
         "nqe_take": (i32, [vp, vp, vp, i32, pvp]),
@@ -526,6 +543,38 @@ class Context:
         farr = (NqeWindowSpec * max(1, len(fs)))(*[NqeWindowSpec(int(f), 0 if c is None else int(c), 2 if fr is None else int(fr)) for f, c, fr in fs])
         h = C.c_void_p()
         self.check(lib().nqe_window_execute(self.handle, table.handle, parr, len(parts), karr, len(ks), farr, len(fs), C.byref(h)))
+        return Table(self, h)
+
+    def window_ex(self, table: "Table", partition_by, order_by, funcs) -> "Table":
+        """nqe_window_execute_ex (quirk Q23): window()'s window and output shape with LAG / LEAD / FIRST_VALUE / LAST_VALUE / NTILE and
+        ROWS BETWEEN frames.  `funcs`: a list of dicts (or NqeWindowSpecEx) with the keys func (WindowFuncEx), column, frame
+        (WindowFrameEx; missing: Range), start, end (ROWS BETWEEN offsets; None: unbounded on that side), param (k of LAG / LEAD, the
+        buckets of NTILE) and default (an int or float written as the column's 8 bytes: float -> f64, negative int -> i64, else u64)"""
+        parts = [int(c) for c in partition_by]
+        ks = [(k, False, True) if isinstance(k, int) else tuple(k) + (False, True)[len(k) - 1:] for k in order_by]
+        specs = []
+        for f in funcs:
+            if isinstance(f, NqeWindowSpecEx):
+                specs.append(f)
+                continue
+            start, end = f.get("start"), f.get("end")
+            s = NqeWindowSpecEx(int(f["func"]), int(f.get("column") or 0), 2 if f.get("frame") is None else int(f["frame"]), 0,
+                                FRAME_UNBOUNDED_PRECEDING if start is None else int(start), FRAME_UNBOUNDED_FOLLOWING if end is None else int(end), int(f.get("param") or 0))
+            d = f.get("default")
+            if d is not None:
+                s.has_default = 1
+                if isinstance(d, float):
+                    s.default_value.f64 = d
+                elif d < 0:
+                    s.default_value.i64 = int(d)
+                else:
+                    s.default_value.u64 = int(d)
+            specs.append(s)
+        parr = (C.c_int32 * max(1, len(parts)))(*parts)
+        karr = (NqeSortKey * max(1, len(ks)))(*[NqeSortKey(int(c), int(bool(d)), int(bool(nf))) for c, d, nf in ks])
+        farr = (NqeWindowSpecEx * max(1, len(specs)))(*specs)
+        h = C.c_void_p()
+        self.check(lib().nqe_window_execute_ex(self.handle, table.handle, parr, len(parts), karr, len(ks), farr, len(specs), C.byref(h)))
         return Table(self, h)
 
     def distinct(self, table: "Table", cols=None) -> "Table":

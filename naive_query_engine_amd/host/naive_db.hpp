@@ -19,6 +19,7 @@
 #include <algorithm>
 #include <cstring>
 #include <fstream>
+#include <functional>
 #include <iterator>
 #include <map>
 #include <memory>
@@ -1100,6 +1101,68 @@ struct PhysicalSortPlan : PhysicalPlan {
 // Like PhysicalSortPlan the input batches are concatenated and ONE batch leaves: the input's columns in input order, then one column per
 // function (row_number(), rank(), dense_rank(), count(x), sum(x), …).  A key or argument that is a bare ColumnExpr is passed by index;
 // any other expression is evaluated into a temporary column that never reaches the output.
+// The body both window plans share: the batches concatenated, keys and arguments resolved to column indices (a bare ColumnExpr by index,
+// any other expression evaluated into a temporary column), `call(ctx, source, partition columns, order keys, argument columns, &out)`,
+// then the input's columns beside the functions' as ONE batch with `out_schema`.  args[f] is null for a function without argument.
+template <typename Call>
+inline std::vector<RecordBatch> run_window_plan(std::vector<RecordBatch> batches, const std::vector<PhysicalExprRef> &partition_by, const std::vector<PhysicalSortExpr> &order_by,
+                                                const std::vector<PhysicalExprRef> &args, const std::function<NaiveSchema(const NaiveSchema &)> &out_schema, Call call) {
+    if (batches.empty()) throw ErrorCode(ErrorCode::NotSupported, "window functions over an empty batch list are not supported on the device path");
+    const ContextRef &ctx = batches[0].ctx();
+    const NaiveSchema &s = batches[0].schema();
+    const NaiveSchema schema = out_schema(s); // (what the plan refuses by its schema is refused before anything runs)
+    auto release = [](nqe_table *p) { nqe_table_release(p); };
+    std::vector<std::shared_ptr<nqe_table>> guards;
+    std::shared_ptr<nqe_table> in = batches[0].shared();
+    if (batches.size() > 1) {
+        std::vector<const nqe_table *> parts;
+        for (auto &b : batches) parts.push_back(b.raw());
+        nqe_table *c = nullptr;
+        ctx->check(nqe_table_concat(ctx->raw(), parts.data(), int32_t(parts.size()), &c));
+        in = std::shared_ptr<nqe_table>(c, release);
+    }
+    const int32_t ncols = nqe_table_num_columns(in.get());
+    std::vector<nqe_column> cols(static_cast<size_t>(ncols)); // `in`'s columns, borrowed; the temporaries follow
+    for (int32_t i = 0; i < ncols; ++i) ctx->check(nqe_table_column(in.get(), i, &cols[size_t(i)]));
+    auto column_of = [&](const PhysicalExprRef &e) {
+        if (const ColumnExpr *c = e->as_column()) return int32_t(c->resolve(s));
+        std::vector<nqe_expr_node> nodes;
+        e->flatten(s, nodes);
+        nqe_table *t = nullptr;
+        ctx->check(nqe_expr_evaluate(ctx->raw(), in.get(), nodes.data(), int32_t(nodes.size()), &t));
+        guards.emplace_back(t, release);
+        nqe_column tc;
+        ctx->check(nqe_table_column(t, 0, &tc));
+        cols.push_back(tc);
+        return int32_t(cols.size()) - 1;
+    };
+    std::vector<int32_t> parts, arg_cols;
+    std::vector<nqe_sort_key> keys;
+    for (auto &e : partition_by) parts.push_back(column_of(e));
+    for (auto &e : order_by) keys.push_back(nqe_sort_key{column_of(e.expr), e.descending ? 1 : 0, e.nulls_first ? 1 : 0});
+    for (auto &e : args) arg_cols.push_back(e ? column_of(e) : 0);
+    const nqe_table *source = in.get();
+    if (cols.size() > size_t(ncols)) {
+        nqe_table *wide = nullptr;
+        ctx->check(nqe_table_create(ctx->raw(), cols.data(), int32_t(cols.size()), &wide));
+        guards.emplace_back(wide, release);
+        source = wide;
+    }
+    nqe_table *w = nullptr;
+    call(ctx, source, parts, keys, arg_cols, &w);
+    std::shared_ptr<nqe_table> win(w, release);
+    // the input's columns beside the functions': a view over both tables, which the batch keeps alive
+    cols.resize(size_t(ncols));
+    for (int32_t i = 0; i < int32_t(args.size()); ++i) {
+        nqe_column c;
+        ctx->check(nqe_table_column(win.get(), i, &c));
+        cols.push_back(c);
+    }
+    nqe_table *both = nullptr;
+    ctx->check(nqe_table_create(ctx->raw(), cols.data(), int32_t(cols.size()), &both));
+    return {batches[0].with_view(schema, both, {in, win})};
+}
+
 struct WindowFunction {
     nqe_window_func func;
     PhysicalExprRef expr; // null for the three ranking functions
@@ -1139,61 +1202,105 @@ struct PhysicalWindowPlan : PhysicalPlan {
     const NaiveSchema &schema() const override { return schema_; }
     std::vector<PhysicalPlanRef> children() const override { return {input}; }
     std::vector<RecordBatch> execute() override {
-        std::vector<RecordBatch> batches = input->execute();
-        if (batches.empty()) throw ErrorCode(ErrorCode::NotSupported, "window functions over an empty batch list are not supported on the device path");
-        const ContextRef &ctx = batches[0].ctx();
-        const NaiveSchema &s = batches[0].schema();
-        auto release = [](nqe_table *p) { nqe_table_release(p); };
-        std::vector<std::shared_ptr<nqe_table>> guards;
-        std::shared_ptr<nqe_table> in = batches[0].shared();
-        if (batches.size() > 1) {
-            std::vector<const nqe_table *> parts;
-            for (auto &b : batches) parts.push_back(b.raw());
-            nqe_table *c = nullptr;
-            ctx->check(nqe_table_concat(ctx->raw(), parts.data(), int32_t(parts.size()), &c));
-            in = std::shared_ptr<nqe_table>(c, release);
+        std::vector<PhysicalExprRef> args;
+        for (auto &f : funcs) args.push_back(f.expr);
+        return run_window_plan(input->execute(), partition_by, order_by, args, [this](const NaiveSchema &below) { return output_schema(below); },
+                               [this](const ContextRef &ctx, const nqe_table *source, const std::vector<int32_t> &parts, const std::vector<nqe_sort_key> &keys, const std::vector<int32_t> &arg_cols,
+                                      nqe_table **w) {
+                                   std::vector<nqe_window_spec> specs;
+                                   for (size_t f = 0; f < funcs.size(); ++f) specs.push_back(nqe_window_spec{int32_t(funcs[f].func), arg_cols[f], int32_t(funcs[f].frame)});
+                                   ctx->check(nqe_window_execute(ctx->raw(), source, parts.data(), int32_t(parts.size()), keys.data(), int32_t(keys.size()), specs.data(), int32_t(specs.size()), w));
+                               });
+    }
+};
+
+// The wider entry (nqe_window_execute_ex): WindowFunction's functions and frames, ROWS BETWEEN start AND end (signed offsets from the current
+// row; nullopt: unbounded on that side), lag / lead by `offset` rows with an optional default of the argument's dtype (Q6: no coercion —
+// another dtype is an IntervalError), first_value / last_value over a frame, ntile over `buckets`.  The value functions' columns are
+// nullable and have the argument's dtype (an expression argument: its left-most column's or literal's; a unary function's Float64).
+struct WindowFunctionEx {
+    nqe_window_func_ex func;
+    PhysicalExprRef expr; // null for the ranking functions and ntile
+    nqe_window_frame_ex frame = NQE_FRAMEX_RANGE;
+    std::optional<int64_t> start, end;
+    int64_t offset = 1, buckets = 1;
+    std::optional<ScalarValue> default_value;
+    WindowFunctionEx(nqe_window_func_ex f, PhysicalExprRef e = nullptr, nqe_window_frame_ex fr = NQE_FRAMEX_RANGE, std::optional<int64_t> s = std::nullopt,
+                     std::optional<int64_t> en = std::nullopt, int64_t off = 1, int64_t b = 1, std::optional<ScalarValue> d = std::nullopt)
+        : func(f), expr(std::move(e)), frame(fr), start(s), end(en), offset(off), buckets(b), default_value(std::move(d)) {
+        if (!no_argument() && !expr) throw ErrorCode(ErrorCode::PlanError, std::string("window function ") + label() + " needs an argument");
+    }
+    static WindowFunctionEx lag(PhysicalExprRef e, int64_t k = 1, std::optional<ScalarValue> d = std::nullopt) { return WindowFunctionEx(NQE_WINX_LAG, std::move(e), NQE_FRAMEX_RANGE, {}, {}, k, 1, std::move(d)); }
+    static WindowFunctionEx lead(PhysicalExprRef e, int64_t k = 1, std::optional<ScalarValue> d = std::nullopt) { return WindowFunctionEx(NQE_WINX_LEAD, std::move(e), NQE_FRAMEX_RANGE, {}, {}, k, 1, std::move(d)); }
+    static WindowFunctionEx ntile(int64_t b) { return WindowFunctionEx(NQE_WINX_NTILE, nullptr, NQE_FRAMEX_RANGE, {}, {}, 1, b); }
+    static WindowFunctionEx between(nqe_window_func_ex f, PhysicalExprRef e, std::optional<int64_t> s, std::optional<int64_t> en) { return WindowFunctionEx(f, std::move(e), NQE_FRAMEX_ROWS_BETWEEN, s, en); }
+    bool no_argument() const { return func <= NQE_WINX_DENSE_RANK || func == NQE_WINX_NTILE; }
+    bool is_value() const { return func >= NQE_WINX_LAG && func <= NQE_WINX_LAST_VALUE; }
+    const char *label() const {
+        static const char *const names[] = {"row_number", "rank", "dense_rank", "count", "sum", "min", "max", "avg", "lag", "lead", "first_value", "last_value", "ntile"};
+        return names[int(func)];
+    }
+    static DataType static_dtype(const PhysicalExprRef &e, const NaiveSchema &schema) {
+        if (const ColumnExpr *c = e->as_column()) return schema.field(c->resolve(schema)).data_type;
+        std::vector<nqe_expr_node> nodes;
+        e->flatten(schema, nodes); // postfix: the first node is the left-most leaf
+        if (!nodes.empty() && nodes.back().kind == NQE_EXPR_UNARY) return DataType::Float64;
+        if (!nodes.empty() && nodes.back().kind == NQE_EXPR_BINARY && (nodes.back().op <= NQE_OP_GT_EQ || nodes.back().op >= NQE_OP_AND)) return DataType::Boolean;
+        if (!nodes.empty() && nodes[0].kind == NQE_EXPR_LITERAL) return DataType(nodes[0].dtype);
+        if (!nodes.empty() && nodes[0].kind == NQE_EXPR_COLUMN) return schema.field(size_t(nodes[0].column)).data_type;
+        return DataType::Float64;
+    }
+    NaiveField data_field(const NaiveSchema &schema) const {
+        if (func == NQE_WINX_NTILE) return NaiveField(std::nullopt, "ntile(" + std::to_string(buckets) + ")", DataType::UInt64, false);
+        if (no_argument()) return NaiveField(std::nullopt, std::string(label()) + "()", DataType::UInt64, false);
+        const ColumnExpr *c = expr->as_column();
+        const std::string arg = c ? schema.field(c->resolve(schema)).name() : std::string("expr");
+        if (is_value()) {
+            const DataType dt = static_dtype(expr, schema);
+            if (default_value && (default_value->is_null || default_value->dtype != dt)) throw ErrorCode(ErrorCode::IntervalError, std::string(label()) + ": the default's type is not the argument's");
+            const bool shift = func == NQE_WINX_LAG || func == NQE_WINX_LEAD;
+            return NaiveField(std::nullopt, std::string(label()) + "(" + arg + (shift ? ", " + std::to_string(offset) : std::string()) + ")", dt, true);
         }
-        const int32_t ncols = nqe_table_num_columns(in.get());
-        std::vector<nqe_column> cols(static_cast<size_t>(ncols)); // `in`'s columns, borrowed; the temporaries follow
-        for (int32_t i = 0; i < ncols; ++i) ctx->check(nqe_table_column(in.get(), i, &cols[size_t(i)]));
-        auto column_of = [&](const PhysicalExprRef &e) {
-            if (const ColumnExpr *c = e->as_column()) return int32_t(c->resolve(s));
-            std::vector<nqe_expr_node> nodes;
-            e->flatten(s, nodes);
-            nqe_table *t = nullptr;
-            ctx->check(nqe_expr_evaluate(ctx->raw(), in.get(), nodes.data(), int32_t(nodes.size()), &t));
-            guards.emplace_back(t, release);
-            nqe_column tc;
-            ctx->check(nqe_table_column(t, 0, &tc));
-            cols.push_back(tc);
-            return int32_t(cols.size()) - 1;
-        };
-        std::vector<int32_t> parts;
-        std::vector<nqe_sort_key> keys;
-        std::vector<nqe_window_spec> specs;
-        for (auto &e : partition_by) parts.push_back(column_of(e));
-        for (auto &e : order_by) keys.push_back(nqe_sort_key{column_of(e.expr), e.descending ? 1 : 0, e.nulls_first ? 1 : 0});
-        for (auto &f : funcs) specs.push_back(nqe_window_spec{int32_t(f.func), f.expr ? column_of(f.expr) : 0, int32_t(f.frame)});
-        const nqe_table *source = in.get();
-        if (cols.size() > size_t(ncols)) {
-            nqe_table *wide = nullptr;
-            ctx->check(nqe_table_create(ctx->raw(), cols.data(), int32_t(cols.size()), &wide));
-            guards.emplace_back(wide, release);
-            source = wide;
-        }
-        nqe_table *w = nullptr;
-        ctx->check(nqe_window_execute(ctx->raw(), source, parts.data(), int32_t(parts.size()), keys.data(), int32_t(keys.size()), specs.data(), int32_t(specs.size()), &w));
-        std::shared_ptr<nqe_table> win(w, release);
-        // the input's columns beside the functions': a view over both tables, which the batch keeps alive
-        cols.resize(size_t(ncols));
-        for (int32_t i = 0; i < int32_t(funcs.size()); ++i) {
-            nqe_column c;
-            ctx->check(nqe_table_column(win.get(), i, &c));
-            cols.push_back(c);
-        }
-        nqe_table *both = nullptr;
-        ctx->check(nqe_table_create(ctx->raw(), cols.data(), int32_t(cols.size()), &both));
-        return {batches[0].with_view(output_schema(s), both, {in, win})};
+        return NaiveField(std::nullopt, std::string(label()) + "(" + arg + ")", func == NQE_WINX_COUNT ? DataType::UInt64 : DataType::Float64, false);
+    }
+    nqe_window_spec_ex spec(int32_t column) const {
+        nqe_window_spec_ex s{};
+        s.func = int32_t(func), s.column = column, s.frame = int32_t(frame);
+        s.start = start ? *start : NQE_FRAME_UNBOUNDED_PRECEDING, s.end = end ? *end : NQE_FRAME_UNBOUNDED_FOLLOWING;
+        s.param = func == NQE_WINX_NTILE ? buckets : offset;
+        if (default_value) s.has_default = 1, s.default_value.u64 = default_value->node.value.u64;
+        return s;
+    }
+};
+struct PhysicalWindowPlanEx : PhysicalPlan {
+    PhysicalPlanRef input;
+    std::vector<PhysicalExprRef> partition_by;
+    std::vector<PhysicalSortExpr> order_by;
+    std::vector<WindowFunctionEx> funcs;
+    NaiveSchema schema_;
+    static PhysicalPlanRef create(PhysicalPlanRef input, std::vector<PhysicalExprRef> partition_by, std::vector<PhysicalSortExpr> order_by, std::vector<WindowFunctionEx> funcs) {
+        auto p = std::make_shared<PhysicalWindowPlanEx>();
+        p->input = std::move(input); p->partition_by = std::move(partition_by); p->order_by = std::move(order_by); p->funcs = std::move(funcs);
+        p->schema_ = p->output_schema(p->input->schema());
+        return p;
+    }
+    NaiveSchema output_schema(const NaiveSchema &below) const {
+        std::vector<NaiveField> fields = below.fields();
+        for (auto &f : funcs) fields.push_back(f.data_field(below));
+        return NaiveSchema(fields);
+    }
+    const NaiveSchema &schema() const override { return schema_; }
+    std::vector<PhysicalPlanRef> children() const override { return {input}; }
+    std::vector<RecordBatch> execute() override {
+        std::vector<PhysicalExprRef> args;
+        for (auto &f : funcs) args.push_back(f.expr);
+        return run_window_plan(input->execute(), partition_by, order_by, args, [this](const NaiveSchema &below) { return output_schema(below); },
+                               [this](const ContextRef &ctx, const nqe_table *source, const std::vector<int32_t> &parts, const std::vector<nqe_sort_key> &keys, const std::vector<int32_t> &arg_cols,
+                                      nqe_table **w) {
+                                   std::vector<nqe_window_spec_ex> specs;
+                                   for (size_t f = 0; f < funcs.size(); ++f) specs.push_back(funcs[f].spec(arg_cols[f]));
+                                   ctx->check(nqe_window_execute_ex(ctx->raw(), source, parts.data(), int32_t(parts.size()), keys.data(), int32_t(keys.size()), specs.data(), int32_t(specs.size()), w));
+                               });
     }
 };
 
@@ -1425,6 +1532,7 @@ inline PhysicalPlanRef rewrite(const PhysicalPlanRef &plan) {
     }
     if (auto srt = std::dynamic_pointer_cast<PhysicalSortPlan>(plan)) return PhysicalSortPlan::create(rewrite(srt->input), srt->sort_exprs, srt->fetch);
     if (auto w = std::dynamic_pointer_cast<PhysicalWindowPlan>(plan)) return PhysicalWindowPlan::create(rewrite(w->input), w->partition_by, w->order_by, w->funcs);
+    if (auto w = std::dynamic_pointer_cast<PhysicalWindowPlanEx>(plan)) return PhysicalWindowPlanEx::create(rewrite(w->input), w->partition_by, w->order_by, w->funcs);
     if (auto d = std::dynamic_pointer_cast<PhysicalDistinctPlan>(plan)) return PhysicalDistinctPlan::create(rewrite(d->input), d->on);
     if (auto so = std::dynamic_pointer_cast<PhysicalSetOpPlan>(plan)) return PhysicalSetOpPlan::create(rewrite(so->left), rewrite(so->right), so->op);
     if (auto o = std::dynamic_pointer_cast<PhysicalOffsetPlan>(plan)) return PhysicalOffsetPlan::create(rewrite(o->input), o->n);

@@ -21,8 +21,8 @@ from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple
 
 from . import capi
-from .arrow_host import AggregateFunc, Column, DType, ErrorCode, Field, RecordBatch, SetOp, Status, WindowFrame, WindowFunc
-from .expression import ColumnExpr, PhysicalExpr
+from .arrow_host import AggregateFunc, Column, DType, ErrorCode, Field, Operator, RecordBatch, ScalarValue, SetOp, Status, WindowFrame, WindowFrameEx, WindowFunc, WindowFuncEx
+from .expression import ColumnExpr, PhysicalBinaryExpr, PhysicalExpr, PhysicalLiteralExpr
 
 NaiveSchema = List[Field]  # src/logical_plan/schema.rs (qualifiers are ignored at physical planning, Q12)
 
@@ -873,6 +873,111 @@ class PhysicalWindowPlan(PhysicalPlan):
         specs = [(f.func, None if f.expr is None else column_of(f.expr), f.frame) for f in self.funcs]
         out = ctx.window(ctx.append_columns(table, temps) if temps else table, parts, keys, specs)
         out_fields = list(fields) + [f.data_field(fields) for f in self.funcs]
+        return [DeviceRecordBatch(out_fields, ctx.append_columns(table, [ctx.project(out, [i]) for i in range(len(self.funcs))]))]
+
+
+# ----------------------------------------------------------------------------- window functions, the wider entry
+_WINDOW_EX_LABELS = {WindowFuncEx.RowNumber: "row_number", WindowFuncEx.Rank: "rank", WindowFuncEx.DenseRank: "dense_rank", WindowFuncEx.Count: "count", WindowFuncEx.Sum: "sum",
+                     WindowFuncEx.Min: "min", WindowFuncEx.Max: "max", WindowFuncEx.Avg: "avg", WindowFuncEx.Lag: "lag", WindowFuncEx.Lead: "lead",
+                     WindowFuncEx.FirstValue: "first_value", WindowFuncEx.LastValue: "last_value", WindowFuncEx.Ntile: "ntile"}
+_WINDOW_EX_NO_ARG = (WindowFuncEx.RowNumber, WindowFuncEx.Rank, WindowFuncEx.DenseRank, WindowFuncEx.Ntile)
+_WINDOW_EX_VALUE = (WindowFuncEx.Lag, WindowFuncEx.Lead, WindowFuncEx.FirstValue, WindowFuncEx.LastValue)
+_COMPARISONS = (Operator.Eq, Operator.NotEq, Operator.Lt, Operator.LtEq, Operator.Gt, Operator.GtEq, Operator.And, Operator.Or)
+
+
+def _static_dtype(expr: PhysicalExpr, schema: NaiveSchema) -> DType:
+    """the dtype an expression evaluates to (Q6: no coercion, so an arithmetic node has its left operand's; a unary function Float64)"""
+    if isinstance(expr, ColumnExpr):
+        return schema[expr.resolve(schema)].dtype
+    if isinstance(expr, PhysicalLiteralExpr):
+        return expr.literal.dtype
+    if isinstance(expr, PhysicalBinaryExpr):
+        return DType.BOOLEAN if expr.op in _COMPARISONS else _static_dtype(expr.left, schema)
+    return DType.FLOAT64
+
+
+class WindowFunctionEx:
+    """one function of nqe_window_execute_ex's window: WindowFunction's functions and frames, ROWS BETWEEN `start` AND `end` (signed
+    offsets from the current row, None: unbounded on that side) with frame WindowFrameEx.RowsBetween, lag / lead over `expr` by `offset`
+    rows with an optional `default` (a ScalarValue of the argument's dtype — Q6: no coercion), first_value / last_value over `expr`
+    and a frame, ntile over `buckets`"""
+
+    def __init__(self, func: WindowFuncEx, expr: Optional[PhysicalExpr] = None, frame: WindowFrameEx = WindowFrameEx.Range, start: Optional[int] = None, end: Optional[int] = None,
+                 offset: int = 1, buckets: int = 1, default: Optional[ScalarValue] = None):
+        self.func, self.expr, self.frame = WindowFuncEx(func), expr, WindowFrameEx(frame)
+        self.start, self.end, self.offset, self.buckets, self.default = start, end, int(offset), int(buckets), default
+        if self.func not in _WINDOW_EX_NO_ARG and expr is None:
+            raise ErrorCode(Status.PlanError, f"window function {_WINDOW_EX_LABELS[self.func]} needs an argument")
+
+    @staticmethod
+    def create(func: WindowFuncEx, expr: Optional[PhysicalExpr] = None, frame: WindowFrameEx = WindowFrameEx.Range, start: Optional[int] = None, end: Optional[int] = None,
+               offset: int = 1, buckets: int = 1, default: Optional[ScalarValue] = None) -> "WindowFunctionEx":
+        return WindowFunctionEx(func, expr, frame, start, end, offset, buckets, default)
+
+    def data_field(self, schema: NaiveSchema) -> Field:
+        label = _WINDOW_EX_LABELS[self.func]
+        if self.func == WindowFuncEx.Ntile:
+            return Field(f"ntile({self.buckets})", DType.UINT64, False)
+        if self.func in _WINDOW_EX_NO_ARG:
+            return Field(f"{label}()", DType.UINT64, False)
+        arg = schema[self.expr.resolve(schema)].name if isinstance(self.expr, ColumnExpr) else repr(self.expr)
+        if self.func in _WINDOW_EX_VALUE:
+            dtype = _static_dtype(self.expr, schema)
+            if self.default is not None and (self.default.dtype != dtype or self.default.value is None):
+                raise ErrorCode(Status.IntervalError, f"{label}: the default is {self.default.dtype.name}, the argument {dtype.name}")
+            return Field(f"{label}({arg}, {self.offset})" if self.func in (WindowFuncEx.Lag, WindowFuncEx.Lead) else f"{label}({arg})", dtype, True)
+        return Field(f"{label}({arg})", DType.UINT64 if self.func == WindowFuncEx.Count else DType.FLOAT64, False)
+
+    def spec(self, column: Optional[int]) -> dict:
+        """the function as Context.window_ex takes it"""
+        d = None if self.default is None else (float(self.default.value) if self.default.dtype == DType.FLOAT64 else int(self.default.value))
+        return {"func": self.func, "column": column, "frame": self.frame, "start": self.start, "end": self.end,
+                "param": self.buckets if self.func == WindowFuncEx.Ntile else self.offset, "default": d}
+
+    def __repr__(self):
+        return f"WindowFunctionEx({self.func.name}, {self.expr!r}, {self.frame.name}, {self.start}, {self.end}, {self.offset}, {self.buckets}, {self.default})"
+
+
+class PhysicalWindowPlanEx(PhysicalPlan):
+    """PhysicalWindowPlan over nqe_window_execute_ex (quirk Q23): the same window, the same shape — the input batches concatenated, ONE
+    batch out with the input's columns and then one column per function, expression keys and arguments evaluated into temporary
+    columns that never reach the output — for WindowFunctionEx's functions; the value functions' columns are nullable and have the
+    argument's dtype."""
+
+    def __init__(self, input: PhysicalPlan, partition_by: Sequence[PhysicalExpr], order_by: Sequence[PhysicalSortExpr], funcs: Sequence[WindowFunctionEx]):
+        self.input, self.partition_by, self.order_by, self.funcs = input, list(partition_by), list(order_by), list(funcs)
+
+    @staticmethod
+    def create(input: PhysicalPlan, partition_by: Sequence[PhysicalExpr], order_by: Sequence[PhysicalSortExpr], funcs: Sequence[WindowFunctionEx]) -> "PhysicalWindowPlanEx":
+        return PhysicalWindowPlanEx(input, partition_by, order_by, funcs)
+
+    def schema(self):
+        s = list(self.input.schema())
+        return s + [f.data_field(s) for f in self.funcs]
+
+    def children(self):
+        return [self.input]
+
+    def execute(self):
+        batches = self.input.execute()
+        if not batches:
+            raise ErrorCode(Status.NotSupported, "window functions over an empty batch list are not supported on the device path")
+        ctx = _ctx_of(batches)
+        fields = batches[0].fields
+        out_fields = list(fields) + [f.data_field(fields) for f in self.funcs]  # (a default of another dtype is refused before anything runs)
+        table = batches[0].table if len(batches) == 1 else ctx.concat([b.table for b in batches])
+        temps = []
+
+        def column_of(expr):
+            if isinstance(expr, ColumnExpr):
+                return expr.resolve(fields)
+            temps.append(ctx.expr_evaluate(table, expr.flatten(fields)))
+            return len(fields) + len(temps) - 1
+
+        parts = [column_of(e) for e in self.partition_by]
+        keys = [(column_of(e.expr), e.descending, e.nulls_first) for e in self.order_by]
+        specs = [f.spec(None if f.expr is None else column_of(f.expr)) for f in self.funcs]
+        out = ctx.window_ex(ctx.append_columns(table, temps) if temps else table, parts, keys, specs)
         return [DeviceRecordBatch(out_fields, ctx.append_columns(table, [ctx.project(out, [i]) for i in range(len(self.funcs))]))]
 
 

@@ -22,7 +22,7 @@ from typing import Dict, List, Optional, Sequence
 
 from .arrow_host import ErrorCode, Field, RecordBatch, Status
 from .physical_plan import (CrossJoin, CsvConfig, CsvTable, DeviceRecordBatch, GroupedAggregatePlan, HashJoin, HashOuterJoin, HashSemiJoin, MemTable, MultiKeyHashJoin, NaiveSchema, NestedLoopJoin, PhysicalAggregatePlan, PhysicalLimitPlan,
-                            PhysicalDistinctPlan, PhysicalOffsetPlan, PhysicalPlan, PhysicalSetOpPlan, PhysicalSortPlan, PhysicalWindowPlan, ProjectionPlan, ScanPlan, SelectionPlan, _ctx_of, _Materialized)
+                            PhysicalDistinctPlan, PhysicalOffsetPlan, PhysicalPlan, PhysicalSetOpPlan, PhysicalSortPlan, PhysicalWindowPlan, PhysicalWindowPlanEx, ProjectionPlan, ScanPlan, SelectionPlan, _ctx_of, _Materialized)
 
 
 # ----------------------------------------------------------------------------- visitor.rs:4-24
@@ -138,6 +138,8 @@ def rewrite(plan: PhysicalPlan) -> PhysicalPlan:
         return PhysicalSortPlan.create(rewrite(plan.input), plan.sort_exprs, plan.fetch)
     if isinstance(plan, PhysicalWindowPlan):  # (a limit above it stays: every row's value depends on its whole partition)
         return PhysicalWindowPlan.create(rewrite(plan.input), plan.partition_by, plan.order_by, plan.funcs)
+    if isinstance(plan, PhysicalWindowPlanEx):  # (the same for the wider entry)
+        return PhysicalWindowPlanEx.create(rewrite(plan.input), plan.partition_by, plan.order_by, plan.funcs)
     if isinstance(plan, PhysicalDistinctPlan):  # (quirk Q24: the node stays, its child is rewritten)
         return PhysicalDistinctPlan.create(rewrite(plan.input), plan.on)
     if isinstance(plan, PhysicalSetOpPlan):
