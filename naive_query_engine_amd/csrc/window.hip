@@ -1,6 +1,9 @@
 // window.hip — window functions as an operator (quirk Q23; the reference has no window expression, logical_plan/expression.rs:22-46):
-// f(...) OVER (PARTITION BY ... ORDER BY ...) for ROW_NUMBER / RANK / DENSE_RANK and Q10's count / sum / min / max / avg over the frames
-// PARTITION, ROWS ... CURRENT ROW and RANGE ... CURRENT ROW.  All functions of a call share one window.
+// f(...) OVER (PARTITION BY ... ORDER BY ...).  All functions of a call share one window.  There is ONE analysis (plan_window_ex,
+// window_ex_plan.hpp) and ONE body (win_execute below) behind both entries.  nqe_window_execute_ex is that pair as it stands;
+// nqe_window_execute — ROW_NUMBER / RANK / DENSE_RANK and Q10's count / sum / min / max / avg over the frames PARTITION, ROWS ... CURRENT
+// ROW and RANGE ... CURRENT ROW, the wider entry's functions 0..7 over its frames 0..2 — is the adapter: plan_window checks its two
+// narrower limits through the same analysis, win_widen zero-extends its specs, and the same body runs.  The stages:
 //
 //   sort         build_sort_permutation (order_by.hip) by (partition keys, order keys): the u32 permutation; no keys, no sort
 //   win_bounds   row perm[i] against row perm[i - 1] on every key: the partition-start and peer-start bitmaps
@@ -10,11 +13,11 @@
 //   win_gather   per distinct value column: the column through the permutation as f64, plus its valid bits
 //   win_scan_*   reduce / carry / apply: the scan of (sum, count, min, max — those the column's functions need) segmented by the
 //                partition-start bitmap; the state at every position
-//   win_emit     ONE launch for every output column: picks the state at i (ROWS), the peer group's last position (RANGE) or the
-//                partition's last position (PARTITION), finishes avg and the ranks, and stores to row perm[i] — the only scatter
-//
-// Out of scope for nqe_window_execute: frames with offsets (n PRECEDING, FOLLOWING); LAG / LEAD / FIRST_VALUE / NTILE — those are
-// nqe_window_execute_ex below, the same stages plus (window_ex_kernels.hpp):
+//   win_emit     ONE launch for every output column of the functions 0..7 over the frames 0..2: picks the state at i (ROWS), the peer
+//                group's last position (RANGE) or the partition's last position (PARTITION), finishes avg and the ranks, and stores to
+//                row perm[i] — the only scatter.  A list of such functions alone (every call of nqe_window_execute) ends here.
+// Frames with offsets (n PRECEDING, FOLLOWING) and LAG / LEAD / FIRST_VALUE / LAST_VALUE / NTILE — nqe_window_execute_ex alone — add
+// (window_ex_kernels.hpp):
 //   win_flags       per distinct width w of a bounded frame: partition starts | block starts, and in reversed positions partition ends |
 //                   block ends (w = 0, a frame that runs to UNBOUNDED FOLLOWING: the partition ends alone)
 //   win_reverse     per value column of such a frame: the gathered column and its valid bits back to front
@@ -60,7 +63,7 @@ void win_scan(nqe_ctx *ctx, int ops, const WinScanArgs &a) {
     }
 }
 
-// ---- the stages of one window call, shared by nqe_window_execute and nqe_window_execute_ex (same launches, same allocation order)
+// ---- the stages of one window call, each called from win_execute alone
 // the sorted order, the two bitmaps and the position arrays
 struct WinOrder {
     SortPermutation sp;
@@ -185,7 +188,7 @@ void win_partition_states(nqe_ctx *ctx, const nqe_table *in, const WinOrder &o, 
     }
 }
 
-// nqe_window_execute's one emit launch over the functions `f` (those of the old entry: functions 0..7 over the frames 0..2)
+// the one emit launch over the functions `e.f`: functions 0..7 over the frames 0..2
 void win_emit_old(nqe_ctx *ctx, const WinOrder &o, WinEmitArgs &e) {
     e.part_first = o.part_first, e.peer_first = o.peer_first, e.peers = o.peers, e.peer_last = o.peer_last, e.part_last = o.part_last;
     e.perm = o.sp.cur;
@@ -193,52 +196,16 @@ void win_emit_old(nqe_ctx *ctx, const WinOrder &o, WinEmitArgs &e) {
     launch(ctx, "win_emit", win_emit_kernel, dim3(unsigned(stream_grid(ctx, o.n, WIN_THREADS))), dim3(WIN_THREADS), 0, e);
 }
 
-} // namespace
-
-} // namespace nqe
-
-using namespace nqe;
-
-nqe_status nqe_window_execute(nqe_ctx *ctx, const nqe_table *in, const int32_t *partition_cols, int32_t num_partition, const nqe_sort_key *order_keys,
-                              int32_t num_order, const nqe_window_spec *funcs, int32_t num_funcs, nqe_table **out) {
-    NQE_API_BEGIN(ctx)
+// the input's column dtypes, as the analysis sees a table (none for a null table: the analysis refuses it first)
+std::vector<int> win_dtypes(const nqe_table *in) {
     std::vector<int> dtypes;
     if (in)
         for (const DevColumn &c : in->cols) dtypes.push_back(c.dtype);
-    const WindowPlan plan = plan_window(ctx != nullptr, in != nullptr, out != nullptr, dtypes.data(), int32_t(dtypes.size()), in ? in->rows : 0, partition_cols, num_partition,
-                                        order_keys, num_order, funcs, num_funcs);
-    const int64_t n = in->rows;
-
-    auto t = std::make_unique<nqe_table>();
-    t->ctx = ctx;
-    t->rows = n;
-    for (int32_t f = 0; f < num_funcs; ++f)
-        t->cols.push_back(make_word_column(ctx, win_is_ranking(funcs[f].func) || funcs[f].func == NQE_WIN_COUNT ? NQE_UINT64 : NQE_FLOAT64, n, false));
-    if (n == 0) {
-        *out = t.release();
-        return NQE_OK;
-    }
-    WinOrder o;
-    win_order(ctx, in, plan.sort_keys, num_partition, plan.positions, o);
-    WinEmitArgs e;
-    std::memset(&e, 0, sizeof(e));
-    std::vector<BufRef> keep;
-    win_partition_states(ctx, in, o, plan.val_cols, plan.val_ops, e.val, keep, nullptr);
-    for (int32_t f = 0; f < num_funcs; ++f) e.f[f] = WinEmitFunc{funcs[f].func, funcs[f].frame, plan.slot[size_t(f)], t->cols[size_t(f)].values->ptr};
-    e.num_funcs = num_funcs;
-    win_emit_old(ctx, o, e);
-    *out = t.release();
-    NQE_API_END()
+    return dtypes;
 }
 
-nqe_status nqe_window_execute_ex(nqe_ctx *ctx, const nqe_table *in, const int32_t *partition_cols, int32_t num_partition, const nqe_sort_key *order_keys,
-                                 int32_t num_order, const nqe_window_spec_ex *funcs, int32_t num_funcs, nqe_table **out) {
-    NQE_API_BEGIN(ctx)
-    std::vector<int> dtypes;
-    if (in)
-        for (const DevColumn &c : in->cols) dtypes.push_back(c.dtype);
-    const WindowExPlan plan = plan_window_ex(ctx != nullptr, in != nullptr, out != nullptr, dtypes.data(), int32_t(dtypes.size()), in ? in->rows : 0, partition_cols,
-                                             num_partition, order_keys, num_order, funcs, num_funcs);
+// The one body of a window call: the output table of `plan` over `funcs` (what plan_window_ex, or plan_window over the widened list, accepted)
+std::unique_ptr<nqe_table> win_execute(nqe_ctx *ctx, const nqe_table *in, int32_t num_partition, const nqe_window_spec_ex *funcs, int32_t num_funcs, const WindowExPlan &plan) {
     const int64_t n = in->rows;
 
     auto t = std::make_unique<nqe_table>();
@@ -248,16 +215,13 @@ nqe_status nqe_window_execute_ex(nqe_ctx *ctx, const nqe_table *in, const int32_
         t->cols.push_back(make_word_column(ctx, plan.out_dtype[size_t(f)], n, n > 0 && winx_is_value(funcs[f].func)));
         if (n == 0) t->cols.back().null_count = 0;
     }
-    if (n == 0) {
-        *out = t.release();
-        return NQE_OK;
-    }
+    if (n == 0) return t;
     WinOrder o;
     win_order(ctx, in, plan.sort_keys, num_partition, plan.positions, o);
     const dim3 block(WIN_THREADS);
     const dim3 row_grid(unsigned(stream_grid(ctx, n, WIN_THREADS)));
 
-    // the partition's forward scans, and nqe_window_execute's own emit for the functions that are its
+    // the partition's forward scans, and the emit of the functions 0..7 over the frames 0..2
     WinEmitArgs e;
     std::memset(&e, 0, sizeof(e));
     std::vector<BufRef> keep;
@@ -368,7 +332,33 @@ nqe_status nqe_window_execute_ex(nqe_ctx *ctx, const nqe_table *in, const int32_
             }
         }
     }
-    *out = t.release();
+    return t;
+}
+
+} // namespace
+
+} // namespace nqe
+
+using namespace nqe;
+
+// the first entry is the adapter: plan_window checks its narrower limits through the one analysis, the widened specs go through the one body
+nqe_status nqe_window_execute(nqe_ctx *ctx, const nqe_table *in, const int32_t *partition_cols, int32_t num_partition, const nqe_sort_key *order_keys,
+                              int32_t num_order, const nqe_window_spec *funcs, int32_t num_funcs, nqe_table **out) {
+    NQE_API_BEGIN(ctx)
+    const std::vector<int> dtypes = win_dtypes(in);
+    const WindowPlan plan = plan_window(ctx != nullptr, in != nullptr, out != nullptr, dtypes.data(), int32_t(dtypes.size()), in ? in->rows : 0, partition_cols, num_partition,
+                                        order_keys, num_order, funcs, num_funcs);
+    *out = win_execute(ctx, in, num_partition, win_widen(funcs, num_funcs).data(), num_funcs, plan).release();
+    NQE_API_END()
+}
+
+nqe_status nqe_window_execute_ex(nqe_ctx *ctx, const nqe_table *in, const int32_t *partition_cols, int32_t num_partition, const nqe_sort_key *order_keys,
+                                 int32_t num_order, const nqe_window_spec_ex *funcs, int32_t num_funcs, nqe_table **out) {
+    NQE_API_BEGIN(ctx)
+    const std::vector<int> dtypes = win_dtypes(in);
+    const WindowExPlan plan = plan_window_ex(ctx != nullptr, in != nullptr, out != nullptr, dtypes.data(), int32_t(dtypes.size()), in ? in->rows : 0, partition_cols,
+                                             num_partition, order_keys, num_order, funcs, num_funcs);
+    *out = win_execute(ctx, in, num_partition, funcs, num_funcs, plan).release();
     NQE_API_END()
 }
 

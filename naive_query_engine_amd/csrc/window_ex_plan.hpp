@@ -1,5 +1,7 @@
-// window_ex_plan.hpp — the host analysis of nqe_window_execute_ex (quirk Q23, window.hip): the argument checks in the order include/nqe.h
-// states them, the clamping and classification of ROWS BETWEEN frames, the grouping of bounded frames by (value column, width), and
+// window_ex_plan.hpp — the one host analysis of the window operator, for both entries (quirk Q23, window.hip): the argument checks in the
+// order include/nqe.h states them, the distinct value columns with their scan operators, the position arrays the function list reads,
+// the clamping and classification of ROWS BETWEEN frames, the grouping of bounded frames by (value column, width), plan_window — the
+// adapter that takes nqe_window_execute's narrower specs through the same analysis — and
 // win_frame_pieces / win_ntile_bucket — the position arithmetic the emit kernels call, written once for host and device so that
 // tests/cpp/test_window_ex_plan.cpp checks on the CPU exactly what the device computes.
 // Plain C++17, no HIP (the two shared functions carry their qualifiers through NQE_WIN_HD).
@@ -131,16 +133,19 @@ struct WindowExPlan {
 
 inline bool winx_is_old(int func, const WinFrameEx &f) { return winx_is_ranking(func) || (winx_is_aggregate(func) && f.cls == WIN_FC_OLD); }
 
-// What nqe_window_execute_ex refuses, in the order of include/nqe.h; launches and allocates nothing.  `dtypes`: the input's column dtypes.
+// The one analysis of a window call: what nqe_window_execute_ex refuses, in the order of include/nqe.h, and the plan of what it does not;
+// launches and allocates nothing.  `dtypes`: the input's column dtypes.  `max_func`, `max_frame`: the last function and frame the entry
+// knows (narrower for nqe_window_execute, see plan_window).
 inline WindowExPlan plan_window_ex(bool ctx_ok, bool in_ok, bool out_ok, const int *dtypes, int32_t num_cols, int64_t rows, const int32_t *partition_cols,
-                                   int32_t num_partition, const nqe_sort_key *order_keys, int32_t num_order, const nqe_window_spec_ex *funcs, int32_t num_funcs) {
+                                   int32_t num_partition, const nqe_sort_key *order_keys, int32_t num_order, const nqe_window_spec_ex *funcs, int32_t num_funcs,
+                                   int max_func = NQE_WINX_NTILE, int max_frame = NQE_FRAMEX_ROWS_BETWEEN) {
     if (!ctx_ok || !in_ok || !out_ok || (num_partition > 0 && !partition_cols) || (num_order > 0 && !order_keys) || (num_funcs > 0 && !funcs))
         fail(NQE_ERR_INVALID_ARGUMENT, "bad arguments");
     for (int32_t f = 0; f < num_funcs; ++f) {
         const nqe_window_spec_ex &s = funcs[f];
-        if (s.func < NQE_WINX_ROW_NUMBER || s.func > NQE_WINX_NTILE) fail(NQE_ERR_INVALID_ARGUMENT, "window: unknown window function");
+        if (s.func < NQE_WINX_ROW_NUMBER || s.func > max_func) fail(NQE_ERR_INVALID_ARGUMENT, "window: unknown window function");
         if (winx_is_framed(s.func)) {
-            if (s.frame < NQE_FRAMEX_PARTITION || s.frame > NQE_FRAMEX_ROWS_BETWEEN) fail(NQE_ERR_INVALID_ARGUMENT, "window: unknown frame");
+            if (s.frame < NQE_FRAMEX_PARTITION || s.frame > max_frame) fail(NQE_ERR_INVALID_ARGUMENT, "window: unknown frame");
             if (s.frame == NQE_FRAMEX_ROWS_BETWEEN) {
                 if (s.start == NQE_FRAME_UNBOUNDED_FOLLOWING) fail(NQE_ERR_INVALID_ARGUMENT, "window: a frame cannot start at UNBOUNDED FOLLOWING");
                 if (s.end == NQE_FRAME_UNBOUNDED_PRECEDING) fail(NQE_ERR_INVALID_ARGUMENT, "window: a frame cannot end at UNBOUNDED PRECEDING");
@@ -231,6 +236,26 @@ inline WindowExPlan plan_window_ex(bool ctx_ok, bool in_ok, bool out_ok, const i
         p.out_dtype.push_back(out_dtype);
     }
     return p;
+}
+
+// ---- nqe_window_execute is nqe_window_execute_ex over functions 0..7 and frames 0..2 (the enum values are equal): its specs widened,
+// every other field zero (a null list stays null) ...
+inline std::vector<nqe_window_spec_ex> win_widen(const nqe_window_spec *funcs, int32_t num_funcs) {
+    std::vector<nqe_window_spec_ex> wide;
+    for (int32_t f = 0; funcs && f < num_funcs; ++f) {
+        nqe_window_spec_ex s{};
+        s.func = funcs[f].func, s.column = funcs[f].column, s.frame = funcs[f].frame;
+        wide.push_back(s);
+    }
+    return wide;
+}
+// ... and the same analysis with the two limits that are narrower for it: the same refusals in the same order, the same plan
+using WindowPlan = WindowExPlan;
+inline WindowPlan plan_window(bool ctx_ok, bool in_ok, bool out_ok, const int *dtypes, int32_t num_cols, int64_t rows, const int32_t *partition_cols, int32_t num_partition,
+                              const nqe_sort_key *order_keys, int32_t num_order, const nqe_window_spec *funcs, int32_t num_funcs) {
+    const std::vector<nqe_window_spec_ex> wide = win_widen(funcs, num_funcs);
+    return plan_window_ex(ctx_ok, in_ok, out_ok, dtypes, num_cols, rows, partition_cols, num_partition, order_keys, num_order, funcs ? wide.data() : nullptr, num_funcs,
+                          NQE_WIN_AVG, NQE_FRAME_RANGE);
 }
 
 } // namespace nqe

@@ -1,8 +1,8 @@
-// window_plan.hpp — the host analysis of the window operator (quirk Q23, window.hip): the argument checks in the order include/nqe.h
-// states them, the distinct value columns of the framed aggregates with the scan operators each needs, which position arrays the
-// function list reads, and the tile and carry counts of the segmented scan.
-// Plain C++17, no HIP and no nqe_table: the input is seen as its column dtypes and row count, so tests/cpp/test_window_plan.cpp
-// compiles this header alone.
+// window_plan.hpp — the constants of the window operator's host analysis (quirk Q23, window.hip): the tile and carry counts of the
+// segmented scan, the scan operators a function needs and the position arrays it reads.  The analysis itself — plan_window_ex, and
+// plan_window, the first entry's adapter onto it — is window_ex_plan.hpp, which needs these constants and which this header includes at
+// its end: whoever includes either header has plan_window and WindowPlan, as before the two analyses became one.
+// Plain C++17, no HIP and no nqe_table.
 #pragma once
 
 #include <cstdint>
@@ -38,7 +38,6 @@ enum WinPos : int {
     WIN_POS_PART_LAST = 16  // the last position of the row's partition: the PARTITION frame
 };
 
-inline bool win_is_ranking(int func) { return func >= NQE_WIN_ROW_NUMBER && func <= NQE_WIN_DENSE_RANK; }
 inline int win_ops_of(int func) {
     switch (func) {
     case NQE_WIN_COUNT: return WIN_OP_COUNT;
@@ -58,60 +57,6 @@ inline int win_positions_of(int func, int frame) {
     }
 }
 
-struct WindowPlan {
-    std::vector<int32_t> val_cols; // the distinct value columns of the framed aggregates, in order of first appearance
-    std::vector<int> val_ops;      // per value column: WinOp bits
-    std::vector<int> slot;         // per function: its index in val_cols, -1 for a ranking function
-    int positions = 0;             // WinPos bits
-    std::vector<nqe_sort_key> sort_keys; // the partition keys with default options, then the order keys: the sorted order
-};
-
-// What nqe_window_execute refuses, in the order of include/nqe.h; launches and allocates nothing.  `dtypes`: the input's column dtypes.
-inline WindowPlan plan_window(bool ctx_ok, bool in_ok, bool out_ok, const int *dtypes, int32_t num_cols, int64_t rows, const int32_t *partition_cols,
-                              int32_t num_partition, const nqe_sort_key *order_keys, int32_t num_order, const nqe_window_spec *funcs, int32_t num_funcs) {
-    if (!ctx_ok || !in_ok || !out_ok || (num_partition > 0 && !partition_cols) || (num_order > 0 && !order_keys) || (num_funcs > 0 && !funcs))
-        fail(NQE_ERR_INVALID_ARGUMENT, "bad arguments");
-    for (int32_t f = 0; f < num_funcs; ++f) {
-        if (funcs[f].func < NQE_WIN_ROW_NUMBER || funcs[f].func > NQE_WIN_AVG) fail(NQE_ERR_INVALID_ARGUMENT, "window: unknown window function");
-        if (!win_is_ranking(funcs[f].func) && (funcs[f].frame < NQE_FRAME_PARTITION || funcs[f].frame > NQE_FRAME_RANGE))
-            fail(NQE_ERR_INVALID_ARGUMENT, "window: unknown frame");
-    }
-    if (num_funcs <= 0) fail(NQE_ERR_PLAN, "window: the list of window functions is empty");
-    if (num_partition > NQE_MAX_WINDOW_KEYS || num_order > NQE_MAX_WINDOW_KEYS)
-        fail(NQE_ERR_NOT_SUPPORTED, "window: at most " + std::to_string(NQE_MAX_WINDOW_KEYS) + " partition keys and as many order keys per call");
-    if (num_funcs > NQE_MAX_WINDOW_FUNCS) fail(NQE_ERR_NOT_SUPPORTED, "window: at most " + std::to_string(NQE_MAX_WINDOW_FUNCS) + " window functions per call");
-    WindowPlan p;
-    for (int32_t k = 0; k < num_partition; ++k) p.sort_keys.push_back(nqe_sort_key{partition_cols[k], 0, 1});
-    for (int32_t k = 0; k < num_order; ++k) p.sort_keys.push_back(order_keys[k]);
-    for (const nqe_sort_key &k : p.sort_keys)
-        if (k.column < 0 || k.column >= num_cols) fail(NQE_ERR_NOT_SUPPORTED, "window: key column index out of range");
-    for (int32_t f = 0; f < num_funcs; ++f)
-        if (!win_is_ranking(funcs[f].func) && (funcs[f].column < 0 || funcs[f].column >= num_cols)) fail(NQE_ERR_NOT_SUPPORTED, "aggregate column index out of range");
-    for (const nqe_sort_key &k : p.sort_keys) {
-        const int dt = dtypes[k.column];
-        if (!(is_word_type(dt) || dt == NQE_BOOLEAN || dt == NQE_UTF8)) fail(NQE_ERR_NOT_SUPPORTED, "order by: keys of this type are not implemented");
-    }
-    for (int32_t f = 0; f < num_funcs; ++f)
-        if (!win_is_ranking(funcs[f].func) && !is_word_type(dtypes[funcs[f].column])) fail(NQE_ERR_NOT_SUPPORTED, "aggregate func for this column type is not supported");
-    // the permutation is u32: refused before anything is allocated
-    if (rows >= (int64_t(1) << 32)) fail(NQE_ERR_NOT_SUPPORTED, "window: " + std::to_string(rows) + " rows, the sort handles fewer than 2^32");
-    for (int32_t f = 0; f < num_funcs; ++f) {
-        const nqe_window_spec &w = funcs[f];
-        p.positions |= win_positions_of(w.func, w.frame);
-        if (win_is_ranking(w.func)) {
-            p.slot.push_back(-1);
-            continue;
-        }
-        size_t j = 0;
-        while (j < p.val_cols.size() && p.val_cols[j] != w.column) ++j;
-        if (j == p.val_cols.size()) {
-            p.val_cols.push_back(w.column);
-            p.val_ops.push_back(0);
-        }
-        p.val_ops[j] |= win_ops_of(w.func);
-        p.slot.push_back(int(j));
-    }
-    return p;
-}
-
 } // namespace nqe
+
+#include "window_ex_plan.hpp" // (behind the constants it reads; it includes this header first when it is the one included)

@@ -1017,6 +1017,60 @@ struct NestedLoopJoin : PhysicalPlan {
     }
 };
 
+// ---------------------------------------------------------------- one table with keys (what ORDER BY, the window plans and DISTINCT begin with)
+inline std::shared_ptr<nqe_table> concat_batches_shared(const ContextRef &ctx, std::vector<RecordBatch> &batches) {
+    if (batches.size() == 1) return batches[0].shared();
+    std::vector<const nqe_table *> parts;
+    for (auto &b : batches) parts.push_back(b.raw());
+    nqe_table *c = nullptr;
+    ctx->check(nqe_table_concat(ctx->raw(), parts.data(), int32_t(parts.size()), &c));
+    return std::shared_ptr<nqe_table>(c, [](nqe_table *p) { nqe_table_release(p); });
+}
+// The batches (not empty) as ONE table whose key and argument expressions are column indices: a bare ColumnExpr is its index, any other
+// expression is evaluated into a temporary column behind the input's.
+struct KeyedTable {
+    const ContextRef ctx;
+    const NaiveSchema &s;
+    const std::shared_ptr<nqe_table> in; // the batches, concatenated when there are several
+    const int32_t ncols;
+    std::vector<nqe_column> cols; // `in`'s columns, borrowed; the temporaries follow
+    std::vector<std::shared_ptr<nqe_table>> guards;
+    static void release(nqe_table *p) { nqe_table_release(p); }
+    explicit KeyedTable(std::vector<RecordBatch> &batches)
+        : ctx(batches[0].ctx()), s(batches[0].schema()), in(concat_batches_shared(ctx, batches)), ncols(nqe_table_num_columns(in.get())), cols(static_cast<size_t>(ncols)) {
+        for (int32_t i = 0; i < ncols; ++i) ctx->check(nqe_table_column(in.get(), i, &cols[size_t(i)]));
+    }
+    int32_t column_of(const PhysicalExprRef &e) {
+        if (const ColumnExpr *c = e->as_column()) return int32_t(c->resolve(s));
+        std::vector<nqe_expr_node> nodes;
+        e->flatten(s, nodes);
+        nqe_table *t = nullptr;
+        ctx->check(nqe_expr_evaluate(ctx->raw(), in.get(), nodes.data(), int32_t(nodes.size()), &t));
+        guards.emplace_back(t, release);
+        nqe_column tc;
+        ctx->check(nqe_table_column(t, 0, &tc));
+        cols.push_back(tc);
+        return int32_t(cols.size()) - 1;
+    }
+    bool has_temporaries() const { return cols.size() > size_t(ncols); }
+    // the table an operator reads: `in` itself when no temporary was made, else `in`'s columns and the temporaries as one wide table
+    const nqe_table *source() {
+        if (!has_temporaries()) return in.get();
+        nqe_table *wide = nullptr;
+        ctx->check(nqe_table_create(ctx->raw(), cols.data(), int32_t(cols.size()), &wide));
+        guards.emplace_back(wide, release);
+        return wide;
+    }
+    // the first ncols columns of `t`, an operator's output over source(): without the temporaries
+    nqe_table *visible(const nqe_table *t) const {
+        std::vector<int32_t> first(static_cast<size_t>(ncols));
+        for (int32_t i = 0; i < ncols; ++i) first[size_t(i)] = i;
+        nqe_table *out = nullptr;
+        ctx->check(nqe_table_project(ctx->raw(), t, first.data(), ncols, &out));
+        return out;
+    }
+};
+
 // ---------------------------------------------------------------- order by (no reference file: sql/planner.rs:159-162 drops the clause)
 // Quirk Q18: what arrow-rs' lexsort_to_indices + take give.  The input batches are concatenated and ONE batch with the input's schema
 // leaves: a stable sort by sort_exprs, first key most significant, cut to `fetch` rows when given.  A bare ColumnExpr key is passed by
@@ -1040,59 +1094,14 @@ struct PhysicalSortPlan : PhysicalPlan {
     std::vector<RecordBatch> execute() override {
         std::vector<RecordBatch> batches = input->execute();
         if (batches.empty()) throw ErrorCode(ErrorCode::NotSupported, "order by over an empty batch list is not supported on the device path");
-        const ContextRef &ctx = batches[0].ctx();
-        const NaiveSchema &s = batches[0].schema();
-        auto release = [](nqe_table *p) { nqe_table_release(p); };
-        std::vector<std::shared_ptr<nqe_table>> guards;
-        nqe_table *in = batches[0].raw();
-        if (batches.size() > 1) {
-            std::vector<const nqe_table *> parts;
-            for (auto &b : batches) parts.push_back(b.raw());
-            nqe_table *c = nullptr;
-            ctx->check(nqe_table_concat(ctx->raw(), parts.data(), int32_t(parts.size()), &c));
-            guards.emplace_back(c, release);
-            in = c;
-        }
-        const int32_t ncols = nqe_table_num_columns(in);
-        std::vector<nqe_column> cols; // `in`'s columns and the temporaries, borrowed, once an expression key asks for them
+        KeyedTable kt(batches);
         std::vector<nqe_sort_key> keys;
-        for (auto &e : sort_exprs) {
-            int32_t col;
-            if (const ColumnExpr *c = e.expr->as_column()) {
-                col = int32_t(c->resolve(s));
-            } else {
-                std::vector<nqe_expr_node> nodes;
-                e.expr->flatten(s, nodes);
-                nqe_table *t = nullptr;
-                ctx->check(nqe_expr_evaluate(ctx->raw(), in, nodes.data(), int32_t(nodes.size()), &t));
-                guards.emplace_back(t, release);
-                if (cols.empty()) {
-                    cols.resize(size_t(ncols));
-                    for (int32_t i = 0; i < ncols; ++i) ctx->check(nqe_table_column(in, i, &cols[size_t(i)]));
-                }
-                nqe_column tc;
-                ctx->check(nqe_table_column(t, 0, &tc));
-                cols.push_back(tc);
-                col = int32_t(cols.size()) - 1;
-            }
-            keys.push_back(nqe_sort_key{col, e.descending ? 1 : 0, e.nulls_first ? 1 : 0});
-        }
-        const int64_t f = fetch ? int64_t(*fetch) : int64_t(-1);
+        for (auto &e : sort_exprs) keys.push_back(nqe_sort_key{kt.column_of(e.expr), e.descending ? 1 : 0, e.nulls_first ? 1 : 0});
         nqe_table *out = nullptr;
-        if (cols.empty()) {
-            ctx->check(nqe_sort_execute(ctx->raw(), in, keys.data(), int32_t(keys.size()), f, &out));
-            return {batches[0].with_table(s, out)};
-        }
-        nqe_table *wide = nullptr;
-        ctx->check(nqe_table_create(ctx->raw(), cols.data(), int32_t(cols.size()), &wide));
-        guards.emplace_back(wide, release);
-        nqe_table *sorted = nullptr;
-        ctx->check(nqe_sort_execute(ctx->raw(), wide, keys.data(), int32_t(keys.size()), f, &sorted));
-        guards.emplace_back(sorted, release);
-        std::vector<int32_t> keep(static_cast<size_t>(ncols));
-        for (int32_t i = 0; i < ncols; ++i) keep[size_t(i)] = i;
-        ctx->check(nqe_table_project(ctx->raw(), sorted, keep.data(), ncols, &out));
-        return {batches[0].with_table(s, out)};
+        kt.ctx->check(nqe_sort_execute(kt.ctx->raw(), kt.source(), keys.data(), int32_t(keys.size()), fetch ? int64_t(*fetch) : int64_t(-1), &out));
+        if (!kt.has_temporaries()) return {batches[0].with_table(kt.s, out)};
+        std::shared_ptr<nqe_table> sorted(out, KeyedTable::release);
+        return {batches[0].with_table(kt.s, kt.visible(sorted.get()))};
     }
 };
 
@@ -1101,66 +1110,48 @@ struct PhysicalSortPlan : PhysicalPlan {
 // Like PhysicalSortPlan the input batches are concatenated and ONE batch leaves: the input's columns in input order, then one column per
 // function (row_number(), rank(), dense_rank(), count(x), sum(x), …).  A key or argument that is a bare ColumnExpr is passed by index;
 // any other expression is evaluated into a temporary column that never reaches the output.
-// The body both window plans share: the batches concatenated, keys and arguments resolved to column indices (a bare ColumnExpr by index,
-// any other expression evaluated into a temporary column), `call(ctx, source, partition columns, order keys, argument columns, &out)`,
-// then the input's columns beside the functions' as ONE batch with `out_schema`.  args[f] is null for a function without argument.
-template <typename Call>
+// Each plan keeps its own C entry, chosen by the type of its functions' spec().
+inline nqe_status window_execute(nqe_ctx *ctx, const nqe_table *in, const std::vector<int32_t> &parts, const std::vector<nqe_sort_key> &keys, const std::vector<nqe_window_spec> &specs,
+                                 nqe_table **out) {
+    return nqe_window_execute(ctx, in, parts.data(), int32_t(parts.size()), keys.data(), int32_t(keys.size()), specs.data(), int32_t(specs.size()), out);
+}
+inline nqe_status window_execute(nqe_ctx *ctx, const nqe_table *in, const std::vector<int32_t> &parts, const std::vector<nqe_sort_key> &keys, const std::vector<nqe_window_spec_ex> &specs,
+                                 nqe_table **out) {
+    return nqe_window_execute_ex(ctx, in, parts.data(), int32_t(parts.size()), keys.data(), int32_t(keys.size()), specs.data(), int32_t(specs.size()), out);
+}
+template <typename Function> inline NaiveSchema window_output_schema(const NaiveSchema &below, const std::vector<Function> &funcs) {
+    std::vector<NaiveField> fields = below.fields();
+    for (auto &f : funcs) fields.push_back(f.data_field(below));
+    return NaiveSchema(fields);
+}
+// The body both window plans share: the batches concatenated, keys and arguments resolved to column indices (KeyedTable), the C entry of
+// the functions' spec type, then the input's columns beside the functions' as ONE batch.
+template <typename Function>
 inline std::vector<RecordBatch> run_window_plan(std::vector<RecordBatch> batches, const std::vector<PhysicalExprRef> &partition_by, const std::vector<PhysicalSortExpr> &order_by,
-                                                const std::vector<PhysicalExprRef> &args, const std::function<NaiveSchema(const NaiveSchema &)> &out_schema, Call call) {
+                                                const std::vector<Function> &funcs) {
     if (batches.empty()) throw ErrorCode(ErrorCode::NotSupported, "window functions over an empty batch list are not supported on the device path");
-    const ContextRef &ctx = batches[0].ctx();
-    const NaiveSchema &s = batches[0].schema();
-    const NaiveSchema schema = out_schema(s); // (what the plan refuses by its schema is refused before anything runs)
-    auto release = [](nqe_table *p) { nqe_table_release(p); };
-    std::vector<std::shared_ptr<nqe_table>> guards;
-    std::shared_ptr<nqe_table> in = batches[0].shared();
-    if (batches.size() > 1) {
-        std::vector<const nqe_table *> parts;
-        for (auto &b : batches) parts.push_back(b.raw());
-        nqe_table *c = nullptr;
-        ctx->check(nqe_table_concat(ctx->raw(), parts.data(), int32_t(parts.size()), &c));
-        in = std::shared_ptr<nqe_table>(c, release);
-    }
-    const int32_t ncols = nqe_table_num_columns(in.get());
-    std::vector<nqe_column> cols(static_cast<size_t>(ncols)); // `in`'s columns, borrowed; the temporaries follow
-    for (int32_t i = 0; i < ncols; ++i) ctx->check(nqe_table_column(in.get(), i, &cols[size_t(i)]));
-    auto column_of = [&](const PhysicalExprRef &e) {
-        if (const ColumnExpr *c = e->as_column()) return int32_t(c->resolve(s));
-        std::vector<nqe_expr_node> nodes;
-        e->flatten(s, nodes);
-        nqe_table *t = nullptr;
-        ctx->check(nqe_expr_evaluate(ctx->raw(), in.get(), nodes.data(), int32_t(nodes.size()), &t));
-        guards.emplace_back(t, release);
-        nqe_column tc;
-        ctx->check(nqe_table_column(t, 0, &tc));
-        cols.push_back(tc);
-        return int32_t(cols.size()) - 1;
-    };
-    std::vector<int32_t> parts, arg_cols;
+    const NaiveSchema schema = window_output_schema(batches[0].schema(), funcs); // (what the plan refuses by its schema is refused before anything runs)
+    KeyedTable kt(batches);
+    const ContextRef &ctx = kt.ctx;
+    std::vector<int32_t> parts;
     std::vector<nqe_sort_key> keys;
-    for (auto &e : partition_by) parts.push_back(column_of(e));
-    for (auto &e : order_by) keys.push_back(nqe_sort_key{column_of(e.expr), e.descending ? 1 : 0, e.nulls_first ? 1 : 0});
-    for (auto &e : args) arg_cols.push_back(e ? column_of(e) : 0);
-    const nqe_table *source = in.get();
-    if (cols.size() > size_t(ncols)) {
-        nqe_table *wide = nullptr;
-        ctx->check(nqe_table_create(ctx->raw(), cols.data(), int32_t(cols.size()), &wide));
-        guards.emplace_back(wide, release);
-        source = wide;
-    }
+    std::vector<decltype(funcs[0].spec(0))> specs;
+    for (auto &e : partition_by) parts.push_back(kt.column_of(e));
+    for (auto &e : order_by) keys.push_back(nqe_sort_key{kt.column_of(e.expr), e.descending ? 1 : 0, e.nulls_first ? 1 : 0});
+    for (auto &f : funcs) specs.push_back(f.spec(f.expr ? kt.column_of(f.expr) : 0)); // (no argument: column 0, which is not read)
     nqe_table *w = nullptr;
-    call(ctx, source, parts, keys, arg_cols, &w);
-    std::shared_ptr<nqe_table> win(w, release);
+    ctx->check(window_execute(ctx->raw(), kt.source(), parts, keys, specs, &w));
+    std::shared_ptr<nqe_table> win(w, KeyedTable::release);
     // the input's columns beside the functions': a view over both tables, which the batch keeps alive
-    cols.resize(size_t(ncols));
-    for (int32_t i = 0; i < int32_t(args.size()); ++i) {
+    std::vector<nqe_column> cols(kt.cols.begin(), kt.cols.begin() + kt.ncols);
+    for (int32_t i = 0; i < int32_t(funcs.size()); ++i) {
         nqe_column c;
         ctx->check(nqe_table_column(win.get(), i, &c));
         cols.push_back(c);
     }
     nqe_table *both = nullptr;
     ctx->check(nqe_table_create(ctx->raw(), cols.data(), int32_t(cols.size()), &both));
-    return {batches[0].with_view(schema, both, {in, win})};
+    return {batches[0].with_view(schema, both, {kt.in, win})};
 }
 
 struct WindowFunction {
@@ -1181,37 +1172,26 @@ struct WindowFunction {
         const std::string arg = c ? schema.field(c->resolve(schema)).name() : std::string("expr");
         return NaiveField(std::nullopt, std::string(label()) + "(" + arg + ")", func == NQE_WIN_COUNT ? DataType::UInt64 : DataType::Float64, false);
     }
+    nqe_window_spec spec(int32_t column) const { return nqe_window_spec{int32_t(func), column, int32_t(frame)}; }
 };
-struct PhysicalWindowPlan : PhysicalPlan {
+// What the two window plans share: the fields and create().  `Plan` is the plan itself, `Function` its function type.
+template <typename Plan, typename Function> struct WindowPlanShell {
     PhysicalPlanRef input;
     std::vector<PhysicalExprRef> partition_by;
     std::vector<PhysicalSortExpr> order_by;
-    std::vector<WindowFunction> funcs;
+    std::vector<Function> funcs;
     NaiveSchema schema_;
-    static PhysicalPlanRef create(PhysicalPlanRef input, std::vector<PhysicalExprRef> partition_by, std::vector<PhysicalSortExpr> order_by, std::vector<WindowFunction> funcs) {
-        auto p = std::make_shared<PhysicalWindowPlan>();
+    static PhysicalPlanRef create(PhysicalPlanRef input, std::vector<PhysicalExprRef> partition_by, std::vector<PhysicalSortExpr> order_by, std::vector<Function> funcs) {
+        auto p = std::make_shared<Plan>();
         p->input = std::move(input); p->partition_by = std::move(partition_by); p->order_by = std::move(order_by); p->funcs = std::move(funcs);
-        p->schema_ = p->output_schema(p->input->schema());
+        p->schema_ = window_output_schema(p->input->schema(), p->funcs);
         return p;
     }
-    NaiveSchema output_schema(const NaiveSchema &below) const {
-        std::vector<NaiveField> fields = below.fields();
-        for (auto &f : funcs) fields.push_back(f.data_field(below));
-        return NaiveSchema(fields);
-    }
+};
+struct PhysicalWindowPlan : PhysicalPlan, WindowPlanShell<PhysicalWindowPlan, WindowFunction> {
     const NaiveSchema &schema() const override { return schema_; }
     std::vector<PhysicalPlanRef> children() const override { return {input}; }
-    std::vector<RecordBatch> execute() override {
-        std::vector<PhysicalExprRef> args;
-        for (auto &f : funcs) args.push_back(f.expr);
-        return run_window_plan(input->execute(), partition_by, order_by, args, [this](const NaiveSchema &below) { return output_schema(below); },
-                               [this](const ContextRef &ctx, const nqe_table *source, const std::vector<int32_t> &parts, const std::vector<nqe_sort_key> &keys, const std::vector<int32_t> &arg_cols,
-                                      nqe_table **w) {
-                                   std::vector<nqe_window_spec> specs;
-                                   for (size_t f = 0; f < funcs.size(); ++f) specs.push_back(nqe_window_spec{int32_t(funcs[f].func), arg_cols[f], int32_t(funcs[f].frame)});
-                                   ctx->check(nqe_window_execute(ctx->raw(), source, parts.data(), int32_t(parts.size()), keys.data(), int32_t(keys.size()), specs.data(), int32_t(specs.size()), w));
-                               });
-    }
+    std::vector<RecordBatch> execute() override { return run_window_plan(input->execute(), partition_by, order_by, funcs); }
 };
 
 // The wider entry (nqe_window_execute_ex): WindowFunction's functions and frames, ROWS BETWEEN start AND end (signed offsets from the current
@@ -1272,36 +1252,10 @@ struct WindowFunctionEx {
         return s;
     }
 };
-struct PhysicalWindowPlanEx : PhysicalPlan {
-    PhysicalPlanRef input;
-    std::vector<PhysicalExprRef> partition_by;
-    std::vector<PhysicalSortExpr> order_by;
-    std::vector<WindowFunctionEx> funcs;
-    NaiveSchema schema_;
-    static PhysicalPlanRef create(PhysicalPlanRef input, std::vector<PhysicalExprRef> partition_by, std::vector<PhysicalSortExpr> order_by, std::vector<WindowFunctionEx> funcs) {
-        auto p = std::make_shared<PhysicalWindowPlanEx>();
-        p->input = std::move(input); p->partition_by = std::move(partition_by); p->order_by = std::move(order_by); p->funcs = std::move(funcs);
-        p->schema_ = p->output_schema(p->input->schema());
-        return p;
-    }
-    NaiveSchema output_schema(const NaiveSchema &below) const {
-        std::vector<NaiveField> fields = below.fields();
-        for (auto &f : funcs) fields.push_back(f.data_field(below));
-        return NaiveSchema(fields);
-    }
+struct PhysicalWindowPlanEx : PhysicalPlan, WindowPlanShell<PhysicalWindowPlanEx, WindowFunctionEx> {
     const NaiveSchema &schema() const override { return schema_; }
     std::vector<PhysicalPlanRef> children() const override { return {input}; }
-    std::vector<RecordBatch> execute() override {
-        std::vector<PhysicalExprRef> args;
-        for (auto &f : funcs) args.push_back(f.expr);
-        return run_window_plan(input->execute(), partition_by, order_by, args, [this](const NaiveSchema &below) { return output_schema(below); },
-                               [this](const ContextRef &ctx, const nqe_table *source, const std::vector<int32_t> &parts, const std::vector<nqe_sort_key> &keys, const std::vector<int32_t> &arg_cols,
-                                      nqe_table **w) {
-                                   std::vector<nqe_window_spec_ex> specs;
-                                   for (size_t f = 0; f < funcs.size(); ++f) specs.push_back(funcs[f].spec(arg_cols[f]));
-                                   ctx->check(nqe_window_execute_ex(ctx->raw(), source, parts.data(), int32_t(parts.size()), keys.data(), int32_t(keys.size()), specs.data(), int32_t(specs.size()), w));
-                               });
-    }
+    std::vector<RecordBatch> execute() override { return run_window_plan(input->execute(), partition_by, order_by, funcs); }
 };
 
 // ---------------------------------------------------------------- DISTINCT and the set operators (no reference file: the planner has no DISTINCT and no set operator)
@@ -1309,14 +1263,6 @@ struct PhysicalWindowPlanEx : PhysicalPlan {
 // column), in input order, with every input column.  PhysicalSetOpPlan: UNION / INTERSECT / EXCEPT, every column a key, left's schema.
 // Like PhysicalSortPlan the input batches are concatenated and ONE batch leaves.  A key that is a bare ColumnExpr is passed by index;
 // any other expression is evaluated into a temporary column that never reaches the output.
-inline std::shared_ptr<nqe_table> concat_batches_shared(const ContextRef &ctx, std::vector<RecordBatch> &batches) {
-    if (batches.size() == 1) return batches[0].shared();
-    std::vector<const nqe_table *> parts;
-    for (auto &b : batches) parts.push_back(b.raw());
-    nqe_table *c = nullptr;
-    ctx->check(nqe_table_concat(ctx->raw(), parts.data(), int32_t(parts.size()), &c));
-    return std::shared_ptr<nqe_table>(c, [](nqe_table *p) { nqe_table_release(p); });
-}
 struct PhysicalDistinctPlan : PhysicalPlan {
     PhysicalPlanRef input;
     std::optional<std::vector<PhysicalExprRef>> on;
@@ -1330,50 +1276,16 @@ struct PhysicalDistinctPlan : PhysicalPlan {
     std::vector<RecordBatch> execute() override {
         std::vector<RecordBatch> batches = input->execute();
         if (batches.empty()) throw ErrorCode(ErrorCode::NotSupported, "distinct over an empty batch list is not supported on the device path");
-        const ContextRef &ctx = batches[0].ctx();
-        const NaiveSchema &s = batches[0].schema();
-        auto release = [](nqe_table *p) { nqe_table_release(p); };
-        std::shared_ptr<nqe_table> in = concat_batches_shared(ctx, batches);
-        nqe_table *out = nullptr;
-        if (!on) {
-            ctx->check(nqe_distinct_execute(ctx->raw(), in.get(), nullptr, 0, &out));
-            return {batches[0].with_table(s, out)};
-        }
-        const int32_t ncols = nqe_table_num_columns(in.get());
-        std::vector<std::shared_ptr<nqe_table>> guards;
-        std::vector<nqe_column> cols(static_cast<size_t>(ncols)); // `in`'s columns, borrowed; the temporaries follow
-        for (int32_t i = 0; i < ncols; ++i) ctx->check(nqe_table_column(in.get(), i, &cols[size_t(i)]));
+        KeyedTable kt(batches);
         std::vector<int32_t> keys;
-        for (auto &e : *on) {
-            if (const ColumnExpr *c = e->as_column()) {
-                keys.push_back(int32_t(c->resolve(s)));
-                continue;
-            }
-            std::vector<nqe_expr_node> nodes;
-            e->flatten(s, nodes);
-            nqe_table *t = nullptr;
-            ctx->check(nqe_expr_evaluate(ctx->raw(), in.get(), nodes.data(), int32_t(nodes.size()), &t));
-            guards.emplace_back(t, release);
-            nqe_column tc;
-            ctx->check(nqe_table_column(t, 0, &tc));
-            cols.push_back(tc);
-            keys.push_back(int32_t(cols.size()) - 1);
-        }
-        if (cols.size() == size_t(ncols)) {
-            ctx->check(nqe_distinct_execute(ctx->raw(), in.get(), keys.data(), int32_t(keys.size()), &out));
-            return {batches[0].with_table(s, out)};
-        }
-        nqe_table *wide = nullptr;
-        ctx->check(nqe_table_create(ctx->raw(), cols.data(), int32_t(cols.size()), &wide));
-        guards.emplace_back(wide, release);
-        ctx->check(nqe_distinct_execute(ctx->raw(), wide, keys.data(), int32_t(keys.size()), &out));
-        std::shared_ptr<nqe_table> all(out, release);
+        if (on)
+            for (auto &e : *on) keys.push_back(kt.column_of(e));
+        nqe_table *out = nullptr;
+        kt.ctx->check(nqe_distinct_execute(kt.ctx->raw(), kt.source(), on ? keys.data() : nullptr, int32_t(keys.size()), &out));
+        if (!kt.has_temporaries()) return {batches[0].with_table(kt.s, out)};
         // the input's columns without the temporaries: a view of the result's first columns, which the batch keeps alive
-        std::vector<int32_t> first(static_cast<size_t>(ncols));
-        for (int32_t i = 0; i < ncols; ++i) first[size_t(i)] = i;
-        nqe_table *visible = nullptr;
-        ctx->check(nqe_table_project(ctx->raw(), all.get(), first.data(), ncols, &visible));
-        return {batches[0].with_view(s, visible, {all})};
+        std::shared_ptr<nqe_table> all(out, KeyedTable::release);
+        return {batches[0].with_view(kt.s, kt.visible(all.get()), {all})};
     }
 };
 struct PhysicalSetOpPlan : PhysicalPlan {

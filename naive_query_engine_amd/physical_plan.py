@@ -160,6 +160,32 @@ def _ctx_of(batches: Sequence[DeviceRecordBatch]) -> "capi.Context":
     return batches[0].table.ctx if batches else capi.default_context()
 
 
+def _one_table(ctx, batches):
+    return batches[0].table if len(batches) == 1 else ctx.concat([b.table for b in batches])
+
+
+class _KeyedTable:
+    """The batches as one table whose key and argument expressions are column indices (run_window_plan's first half in the C++ mirror):
+    a bare ColumnExpr is its index, any other expression is evaluated into a temporary column behind the input's."""
+
+    def __init__(self, ctx, batches, fields):
+        self.ctx, self.fields, self.table, self.temps = ctx, fields, _one_table(ctx, batches), []
+
+    def column_of(self, expr: PhysicalExpr) -> int:
+        if isinstance(expr, ColumnExpr):
+            return expr.resolve(self.fields)
+        self.temps.append(self.ctx.expr_evaluate(self.table, expr.flatten(self.fields)))
+        return len(self.fields) + len(self.temps) - 1
+
+    def source(self):
+        """the table an operator reads: the input itself when no temporary was made"""
+        return self.ctx.append_columns(self.table, self.temps) if self.temps else self.table
+
+    def without_temps(self, out):
+        """an output with source()'s columns, the temporaries projected away"""
+        return self.ctx.project(out, list(range(len(self.fields)))) if self.temps else out
+
+
 class SelectionPlan(PhysicalPlan):
     """src/physical_plan/selection.rs:23-112"""
 
@@ -395,7 +421,7 @@ class PhysicalAggregatePlan(PhysicalPlan):
             out, _ = ctx.aggregate_merge([merged_state], None, aggs)
             return [DeviceRecordBatch(out_fields, out)]
         # grouped: concat_batches, then group by group_expr[0] only (:143-148)
-        table = batches[0].table if len(batches) == 1 else ctx.concat([b.table for b in batches])
+        table = _one_table(ctx, batches)
         key = self.group_expr[0].flatten(fields)
         out = ctx.aggregate(table, aggs, group_nodes=key, pred_nodes=pred)
         return [DeviceRecordBatch(out_fields, out)]
@@ -443,7 +469,7 @@ class GroupedAggregatePlan(PhysicalPlan):
             raise ErrorCode(Status.NotSupported, "aggregate over an empty batch list is not supported on the device path")
         ctx = _ctx_of(batches)
         fields = batches[0].fields
-        table = batches[0].table if len(batches) == 1 else ctx.concat([b.table for b in batches])
+        table = _one_table(ctx, batches)
         aggs = [(op.func, op.col_expr.resolve(fields)) for op in self.aggr_ops]
         pred = pred_expr.flatten(fields) if pred_expr is not None else None
         out = ctx.group_aggregate(table, [e.flatten(fields) for e in self.group_expr], aggs, pred_nodes=pred)
@@ -497,7 +523,7 @@ class HashJoin(PhysicalPlan):
         ctx = _ctx_of(lb or rb)
         if not lb:
             raise ErrorCode(Status.NotSupported, "join with an empty left batch list is not supported on the device path")
-        ltab = lb[0].table if len(lb) == 1 else ctx.concat([b.table for b in lb])  # concat_batches (:132)
+        ltab = _one_table(ctx, lb)  # concat_batches (:132)
         lkey = ColumnExpr.try_create(self.on[0][0].name, None).resolve(lb[0].fields)  # by NAME, first match (:134-136)
         # Q11: build() pushes the row indices into the SAME map again on every execute(), so the k-th execute() emits each
         # match k times, in the order [matches of the first build..., of the second...].  A build side of k copies of the
@@ -547,7 +573,7 @@ class HashOuterJoin(PhysicalPlan):
         ctx = _ctx_of(lb or rb)
         if not lb:
             raise ErrorCode(Status.NotSupported, "join with an empty left batch list is not supported on the device path")
-        ltab = lb[0].table if len(lb) == 1 else ctx.concat([b.table for b in lb])  # concat_batches (:132)
+        ltab = _one_table(ctx, lb)  # concat_batches (:132)
         lkey = ColumnExpr.try_create(self.on[0][0].name, None).resolve(lb[0].fields)  # by NAME, first match (:134-136)
         jt = ctx.hash_join_build(ltab, lkey)
         marks = ctx.join_marks(jt) if self.join_type == JoinType.Left else None
@@ -601,7 +627,7 @@ class MultiKeyHashJoin(PhysicalPlan):
         ctx = _ctx_of(lb or rb)
         if not lb:
             raise ErrorCode(Status.NotSupported, "join with an empty left batch list is not supported on the device path")
-        ltab = lb[0].table if len(lb) == 1 else ctx.concat([b.table for b in lb])  # concat_batches (:132)
+        ltab = _one_table(ctx, lb)  # concat_batches (:132)
         lkeys = [ColumnExpr.try_create(l.name, None).resolve(lb[0].fields) for l, _ in self.on]  # by NAME, first match (:134-136)
         jt = ctx.hash_join_build_keys(ltab, lkeys)
         marks = ctx.join_marks(jt) if self.join_type == JoinType.Left else None
@@ -660,7 +686,7 @@ class HashSemiJoin(PhysicalPlan):
         ctx = _ctx_of(lb or rb)
         if not lb:
             raise ErrorCode(Status.NotSupported, "join with an empty left batch list is not supported on the device path")
-        ltab = lb[0].table if len(lb) == 1 else ctx.concat([b.table for b in lb])  # concat_batches (:132)
+        ltab = _one_table(ctx, lb)  # concat_batches (:132)
         lkeys = [ColumnExpr.try_create(l.name, None).resolve(lb[0].fields) for l, _ in self.on]  # by NAME, first match (:134-136)
         jt = ctx.hash_join_build_keys(ltab, lkeys)
         build_side = self.semi_type in (SemiJoinType.BuildSemi, SemiJoinType.BuildAnti)
@@ -788,63 +814,51 @@ class PhysicalSortPlan(PhysicalPlan):
             raise ErrorCode(Status.NotSupported, "order by over an empty batch list is not supported on the device path")
         ctx = _ctx_of(batches)
         fields = batches[0].fields
-        table = batches[0].table if len(batches) == 1 else ctx.concat([b.table for b in batches])
-        keys, temps = [], []
-        for e in self.sort_exprs:
-            if isinstance(e.expr, ColumnExpr):
-                col = e.expr.resolve(fields)
-            else:
-                temps.append(ctx.expr_evaluate(table, e.expr.flatten(fields)))
-                col = len(fields) + len(temps) - 1
-            keys.append((col, e.descending, e.nulls_first))
-        if not temps:
-            return [DeviceRecordBatch(fields, ctx.order_by(table, keys, self.fetch))]
-        out = ctx.order_by(ctx.append_columns(table, temps), keys, self.fetch)
-        return [DeviceRecordBatch(fields, ctx.project(out, list(range(len(fields)))))]
+        kt = _KeyedTable(ctx, batches, fields)
+        keys = [(kt.column_of(e.expr), e.descending, e.nulls_first) for e in self.sort_exprs]
+        return [DeviceRecordBatch(fields, kt.without_temps(ctx.order_by(kt.source(), keys, self.fetch)))]
 
 
 # ----------------------------------------------------------------------------- window functions
-_WINDOW_LABELS = {WindowFunc.RowNumber: "row_number", WindowFunc.Rank: "rank", WindowFunc.DenseRank: "dense_rank", WindowFunc.Count: "count",
-                  WindowFunc.Sum: "sum", WindowFunc.Min: "min", WindowFunc.Max: "max", WindowFunc.Avg: "avg"}
-_WINDOW_RANKING = (WindowFunc.RowNumber, WindowFunc.Rank, WindowFunc.DenseRank)
-
-
 class WindowFunction:
     """one function of a window: ROW_NUMBER / RANK / DENSE_RANK (no argument, no frame) or one of Q10's count / sum / min / max / avg
     over `expr` and the rows of `frame` (default: RANGE ... CURRENT ROW, SQL's default with ORDER BY)"""
 
     def __init__(self, func: WindowFunc, expr: Optional[PhysicalExpr] = None, frame: WindowFrame = WindowFrame.Range):
         self.func, self.expr, self.frame = WindowFunc(func), expr, WindowFrame(frame)
-        if self.func not in _WINDOW_RANKING and expr is None:
-            raise ErrorCode(Status.PlanError, f"window function {_WINDOW_LABELS[self.func]} needs an argument")
+        self._wide()  # (refuses a missing argument)
+
+    def _wide(self) -> "WindowFunctionEx":
+        """the same function of the wider entry (the enum values are equal): its argument check and its field are this one's"""
+        return WindowFunctionEx(int(self.func), self.expr, int(self.frame))
 
     @staticmethod
     def create(func: WindowFunc, expr: Optional[PhysicalExpr] = None, frame: WindowFrame = WindowFrame.Range) -> "WindowFunction":
         return WindowFunction(func, expr, frame)
 
     def data_field(self, schema: NaiveSchema) -> Field:
-        label = _WINDOW_LABELS[self.func]
-        if self.func in _WINDOW_RANKING:
-            return Field(f"{label}()", DType.UINT64, False)
-        arg = schema[self.expr.resolve(schema)].name if isinstance(self.expr, ColumnExpr) else repr(self.expr)
-        return Field(f"{label}({arg})", DType.UINT64 if self.func == WindowFunc.Count else DType.FLOAT64, False)
+        return self._wide().data_field(schema)
+
+    def spec(self, column: Optional[int]) -> tuple:
+        """the function as Context.window takes it"""
+        return (self.func, column, self.frame)
 
     def __repr__(self):
         return f"WindowFunction({self.func.name}, {self.expr!r}, {self.frame.name})"
 
 
-class PhysicalWindowPlan(PhysicalPlan):
-    """f(...) OVER (PARTITION BY partition_by ORDER BY order_by) for every function of `funcs` (quirk Q23; the reference has no window
-    expression, logical_plan/expression.rs:22-46): all functions share the one window.  Like PhysicalSortPlan the input batches are
-    concatenated and ONE batch leaves: the input's columns in input order, then one column per function.  A key or argument that is a
-    bare ColumnExpr is passed by index; any other expression is evaluated into a temporary column that never reaches the output."""
+class _WindowPlan(PhysicalPlan):
+    """what the two window plans share: everything but the Context method `_entry` and the function type, whose spec() that method takes"""
 
-    def __init__(self, input: PhysicalPlan, partition_by: Sequence[PhysicalExpr], order_by: Sequence[PhysicalSortExpr], funcs: Sequence[WindowFunction]):
+    _entry: str
+    _fields_first = False  # whether a function's field can be refused, which then happens before anything runs
+
+    def __init__(self, input: PhysicalPlan, partition_by: Sequence[PhysicalExpr], order_by: Sequence[PhysicalSortExpr], funcs: Sequence):
         self.input, self.partition_by, self.order_by, self.funcs = input, list(partition_by), list(order_by), list(funcs)
 
-    @staticmethod
-    def create(input: PhysicalPlan, partition_by: Sequence[PhysicalExpr], order_by: Sequence[PhysicalSortExpr], funcs: Sequence[WindowFunction]) -> "PhysicalWindowPlan":
-        return PhysicalWindowPlan(input, partition_by, order_by, funcs)
+    @classmethod
+    def create(cls, input: PhysicalPlan, partition_by: Sequence[PhysicalExpr], order_by: Sequence[PhysicalSortExpr], funcs: Sequence):
+        return cls(input, partition_by, order_by, funcs)
 
     def schema(self):
         s = list(self.input.schema())
@@ -859,21 +873,24 @@ class PhysicalWindowPlan(PhysicalPlan):
             raise ErrorCode(Status.NotSupported, "window functions over an empty batch list are not supported on the device path")
         ctx = _ctx_of(batches)
         fields = batches[0].fields
-        table = batches[0].table if len(batches) == 1 else ctx.concat([b.table for b in batches])
-        temps = []
+        out_fields = list(fields) + [f.data_field(fields) for f in self.funcs] if self._fields_first else None
+        kt = _KeyedTable(ctx, batches, fields)
+        parts = [kt.column_of(e) for e in self.partition_by]
+        keys = [(kt.column_of(e.expr), e.descending, e.nulls_first) for e in self.order_by]
+        specs = [f.spec(None if f.expr is None else kt.column_of(f.expr)) for f in self.funcs]
+        out = getattr(ctx, self._entry)(kt.source(), parts, keys, specs)
+        out_fields = out_fields or list(fields) + [f.data_field(fields) for f in self.funcs]
+        return [DeviceRecordBatch(out_fields, ctx.append_columns(kt.table, [ctx.project(out, [i]) for i in range(len(self.funcs))]))]
 
-        def column_of(expr):
-            if isinstance(expr, ColumnExpr):
-                return expr.resolve(fields)
-            temps.append(ctx.expr_evaluate(table, expr.flatten(fields)))
-            return len(fields) + len(temps) - 1
 
-        parts = [column_of(e) for e in self.partition_by]
-        keys = [(column_of(e.expr), e.descending, e.nulls_first) for e in self.order_by]
-        specs = [(f.func, None if f.expr is None else column_of(f.expr), f.frame) for f in self.funcs]
-        out = ctx.window(ctx.append_columns(table, temps) if temps else table, parts, keys, specs)
-        out_fields = list(fields) + [f.data_field(fields) for f in self.funcs]
-        return [DeviceRecordBatch(out_fields, ctx.append_columns(table, [ctx.project(out, [i]) for i in range(len(self.funcs))]))]
+class PhysicalWindowPlan(_WindowPlan):
+    """f(...) OVER (PARTITION BY partition_by ORDER BY order_by) for every WindowFunction of `funcs`, through nqe_window_execute (quirk
+    Q23; the reference has no window expression, logical_plan/expression.rs:22-46): all functions share the one window.  Like
+    PhysicalSortPlan the input batches are concatenated and ONE batch leaves: the input's columns in input order, then one column per
+    function.  A key or argument that is a bare ColumnExpr is passed by index; any other expression is evaluated into a temporary
+    column that never reaches the output."""
+
+    _entry = "window"
 
 
 # ----------------------------------------------------------------------------- window functions, the wider entry
@@ -938,54 +955,14 @@ class WindowFunctionEx:
         return f"WindowFunctionEx({self.func.name}, {self.expr!r}, {self.frame.name}, {self.start}, {self.end}, {self.offset}, {self.buckets}, {self.default})"
 
 
-class PhysicalWindowPlanEx(PhysicalPlan):
-    """PhysicalWindowPlan over nqe_window_execute_ex (quirk Q23): the same window, the same shape — the input batches concatenated, ONE
-    batch out with the input's columns and then one column per function, expression keys and arguments evaluated into temporary
-    columns that never reach the output — for WindowFunctionEx's functions; the value functions' columns are nullable and have the
-    argument's dtype."""
+class PhysicalWindowPlanEx(_WindowPlan):
+    """PhysicalWindowPlan over nqe_window_execute_ex (quirk Q23): the same window, the same shape, for WindowFunctionEx's functions; the
+    value functions' columns are nullable and have the argument's dtype, and a default of another dtype is refused before anything runs."""
 
-    def __init__(self, input: PhysicalPlan, partition_by: Sequence[PhysicalExpr], order_by: Sequence[PhysicalSortExpr], funcs: Sequence[WindowFunctionEx]):
-        self.input, self.partition_by, self.order_by, self.funcs = input, list(partition_by), list(order_by), list(funcs)
-
-    @staticmethod
-    def create(input: PhysicalPlan, partition_by: Sequence[PhysicalExpr], order_by: Sequence[PhysicalSortExpr], funcs: Sequence[WindowFunctionEx]) -> "PhysicalWindowPlanEx":
-        return PhysicalWindowPlanEx(input, partition_by, order_by, funcs)
-
-    def schema(self):
-        s = list(self.input.schema())
-        return s + [f.data_field(s) for f in self.funcs]
-
-    def children(self):
-        return [self.input]
-
-    def execute(self):
-        batches = self.input.execute()
-        if not batches:
-            raise ErrorCode(Status.NotSupported, "window functions over an empty batch list are not supported on the device path")
-        ctx = _ctx_of(batches)
-        fields = batches[0].fields
-        out_fields = list(fields) + [f.data_field(fields) for f in self.funcs]  # (a default of another dtype is refused before anything runs)
-        table = batches[0].table if len(batches) == 1 else ctx.concat([b.table for b in batches])
-        temps = []
-
-        def column_of(expr):
-            if isinstance(expr, ColumnExpr):
-                return expr.resolve(fields)
-            temps.append(ctx.expr_evaluate(table, expr.flatten(fields)))
-            return len(fields) + len(temps) - 1
-
-        parts = [column_of(e) for e in self.partition_by]
-        keys = [(column_of(e.expr), e.descending, e.nulls_first) for e in self.order_by]
-        specs = [f.spec(None if f.expr is None else column_of(f.expr)) for f in self.funcs]
-        out = ctx.window_ex(ctx.append_columns(table, temps) if temps else table, parts, keys, specs)
-        return [DeviceRecordBatch(out_fields, ctx.append_columns(table, [ctx.project(out, [i]) for i in range(len(self.funcs))]))]
+    _entry, _fields_first = "window_ex", True
 
 
 # ----------------------------------------------------------------------------- DISTINCT and the set operators
-def _one_table(ctx, batches):
-    return batches[0].table if len(batches) == 1 else ctx.concat([b.table for b in batches])
-
-
 class PhysicalDistinctPlan(PhysicalPlan):
     """SELECT DISTINCT (quirk Q24; the reference's planner has no DISTINCT): the rows that are the first occurrence of their tuple
     over the expressions `on` (None: every column), in input order, with every input column.  Like PhysicalSortPlan the input batches
@@ -1011,20 +988,11 @@ class PhysicalDistinctPlan(PhysicalPlan):
             raise ErrorCode(Status.NotSupported, "distinct over an empty batch list is not supported on the device path")
         ctx = _ctx_of(batches)
         fields = batches[0].fields
-        table = _one_table(ctx, batches)
+        kt = _KeyedTable(ctx, batches, fields)
         if self.on is None:
-            return [DeviceRecordBatch(fields, ctx.distinct(table))]
-        temps, cols = [], []
-        for expr in self.on:
-            if isinstance(expr, ColumnExpr):
-                cols.append(expr.resolve(fields))
-            else:
-                temps.append(ctx.expr_evaluate(table, expr.flatten(fields)))
-                cols.append(len(fields) + len(temps) - 1)
-        if not temps:
-            return [DeviceRecordBatch(fields, ctx.distinct(table, cols))]
-        out = ctx.distinct(ctx.append_columns(table, temps), cols)
-        return [DeviceRecordBatch(fields, ctx.project(out, list(range(len(fields)))))]
+            return [DeviceRecordBatch(fields, ctx.distinct(kt.table))]
+        cols = [kt.column_of(expr) for expr in self.on]
+        return [DeviceRecordBatch(fields, kt.without_temps(ctx.distinct(kt.source(), cols)))]
 
 
 class PhysicalSetOpPlan(PhysicalPlan):

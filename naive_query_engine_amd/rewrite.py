@@ -136,10 +136,8 @@ def rewrite(plan: PhysicalPlan) -> PhysicalPlan:
         return PhysicalLimitPlan.create(rewrite(plan.input), plan.n)
     if isinstance(plan, PhysicalSortPlan):
         return PhysicalSortPlan.create(rewrite(plan.input), plan.sort_exprs, plan.fetch)
-    if isinstance(plan, PhysicalWindowPlan):  # (a limit above it stays: every row's value depends on its whole partition)
-        return PhysicalWindowPlan.create(rewrite(plan.input), plan.partition_by, plan.order_by, plan.funcs)
-    if isinstance(plan, PhysicalWindowPlanEx):  # (the same for the wider entry)
-        return PhysicalWindowPlanEx.create(rewrite(plan.input), plan.partition_by, plan.order_by, plan.funcs)
+    if isinstance(plan, (PhysicalWindowPlan, PhysicalWindowPlanEx)):  # (a limit above it stays: every row's value depends on its whole partition)
+        return type(plan).create(rewrite(plan.input), plan.partition_by, plan.order_by, plan.funcs)  # each entry's plan stays its own class
     if isinstance(plan, PhysicalDistinctPlan):  # (quirk Q24: the node stays, its child is rewritten)
         return PhysicalDistinctPlan.create(rewrite(plan.input), plan.on)
     if isinstance(plan, PhysicalSetOpPlan):

@@ -1,6 +1,7 @@
-// The host analysis of the window operator (naive_query_engine_amd/csrc/window_plan.hpp) on the CPU: every refusal in the order
-// include/nqe.h states, the distinct value columns with their scan operators, the position arrays a function list reads, and the tile
-// and carry counts.  Includes that header alone.
+// The host analysis of the window operator as nqe_window_execute sees it (plan_window, the adapter of
+// naive_query_engine_amd/csrc/window_ex_plan.hpp onto plan_window_ex) on the CPU: every refusal in the order include/nqe.h states, the
+// adapter's boundary against the wider entry, the distinct value columns with their scan operators, the position arrays a function list
+// reads, and the tile and carry counts (window_plan.hpp).  Includes window_plan.hpp alone, which brings the analysis with it.
 //   g++ -std=c++17 -I naive_query_engine_amd/csrc tests/cpp/test_window_plan.cpp && ./a.out
 #include <cstdio>
 #include <string>
@@ -153,6 +154,61 @@ static void test_plan() {
     CHECK(win_ops_of(NQE_WIN_COUNT) == WIN_OP_COUNT && win_ops_of(NQE_WIN_AVG) == (WIN_OP_SUM | WIN_OP_COUNT) && win_ops_of(NQE_WIN_RANK) == 0);
 }
 
+// plan_window is plan_window_ex behind two narrower limits: what lies past them is refused with the first entry's messages and
+// precedence, and what lies within gives the wider entry's plan of the widened list
+static void test_adapter_boundary() {
+    std::string msg;
+    for (int bad : {int(NQE_WINX_LAG), int(NQE_WINX_NTILE), -1}) { // 8 and 12 are functions of the wider entry only
+        Call c; c.funcs = {{bad, F, NQE_FRAME_ROWS}};
+        CHECK(status(c, &msg) == NQE_ERR_INVALID_ARGUMENT && msg == "window: unknown window function");
+    }
+    {
+        Call c; c.funcs = {{NQE_WIN_SUM, F, NQE_FRAMEX_ROWS_BETWEEN}}; // frame 3 is the wider entry's
+        CHECK(status(c, &msg) == NQE_ERR_INVALID_ARGUMENT && msg == "window: unknown frame");
+        Call r; r.funcs = {{NQE_WIN_RANK, 0, 99}}; // a ranking function's frame is not read
+        CHECK(status(r) == NQE_OK);
+    }
+    {
+        Call c; c.funcs = {{NQE_WIN_SUM, F, 3}, {99, 0, 0}}; // per function in list order: the first function's frame
+        CHECK(status(c, &msg) == NQE_ERR_INVALID_ARGUMENT && msg == "window: unknown frame");
+        Call d = c; d.ctx = false; // "bad arguments" before anything per function
+        CHECK(status(d, &msg) == NQE_ERR_INVALID_ARGUMENT && msg == "bad arguments");
+        Call e = c; e.null_parts = true; e.num_parts = 1;
+        CHECK(status(e, &msg) == NQE_ERR_INVALID_ARGUMENT && msg == "bad arguments");
+        Call f; f.null_funcs = true; f.num_funcs = 0; // an empty list may be a null pointer
+        CHECK(status(f, &msg) == NQE_ERR_PLAN && msg == "window: the list of window functions is empty");
+    }
+    // one list through both analyses
+    Call c;
+    c.parts = {S, I};
+    c.order = {{F, 1, 0}, {B, 0, 1}};
+    c.funcs = {{NQE_WIN_AVG, F, NQE_FRAME_RANGE}, {NQE_WIN_RANK, 77, 77},         {NQE_WIN_MIN, U, NQE_FRAME_PARTITION},
+               {NQE_WIN_COUNT, F, NQE_FRAME_ROWS}, {NQE_WIN_DENSE_RANK, 0, 0}, {NQE_WIN_MAX, I, NQE_FRAME_ROWS}, {NQE_WIN_ROW_NUMBER, 0, 0}};
+    WindowPlan p;
+    CHECK(status(c, nullptr, &p) == NQE_OK);
+    const std::vector<nqe_window_spec_ex> wide = win_widen(c.funcs.data(), int32_t(c.funcs.size()));
+    CHECK(wide.size() == c.funcs.size());
+    for (size_t f = 0; f < wide.size(); ++f) {
+        const nqe_window_spec_ex &s = wide[f];
+        CHECK(s.func == c.funcs[f].func && s.column == c.funcs[f].column && s.frame == c.funcs[f].frame);
+        CHECK(s.has_default == 0 && s.start == 0 && s.end == 0 && s.param == 0 && s.default_value.u64 == 0);
+    }
+    CHECK(win_widen(nullptr, 3).empty());
+    const WindowExPlan x = plan_window_ex(true, true, true, kDtypes, NCOLS, c.rows, c.parts.data(), int32_t(c.parts.size()), c.order.data(), int32_t(c.order.size()), wide.data(),
+                                          int32_t(wide.size()));
+    CHECK(p.sort_keys.size() == x.sort_keys.size());
+    for (size_t k = 0; k < p.sort_keys.size() && k < x.sort_keys.size(); ++k)
+        CHECK(p.sort_keys[k].column == x.sort_keys[k].column && p.sort_keys[k].descending == x.sort_keys[k].descending && p.sort_keys[k].nulls_first == x.sort_keys[k].nulls_first);
+    CHECK(p.positions == x.positions && p.val_cols == x.val_cols && p.val_ops == x.val_ops && p.slot == x.slot);
+    CHECK(p.positions == (WIN_POS_PART_FIRST | WIN_POS_PEER_FIRST | WIN_POS_PEER_COUNT | WIN_POS_PEER_LAST | WIN_POS_PART_LAST));
+    CHECK((p.val_cols == std::vector<int32_t>{F, U, I}) && (p.slot == std::vector<int>{0, -1, 1, 0, -1, 2, -1}));
+    for (const WindowExPlan *q : {static_cast<const WindowExPlan *>(&p), &x}) {
+        CHECK(q->any_old && !q->any_frame && !q->any_value && q->rev_cols.empty() && q->groups.empty());
+        CHECK(q->frame.size() == c.funcs.size());
+        for (const WinFrameEx &fr : q->frame) CHECK(fr.cls == WIN_FC_OLD);
+    }
+}
+
 static void test_tiles() {
     static_assert(WIN_TILE == int64_t(WIN_THREADS) * WIN_ITEMS, "a tile is one workgroup's rows");
     const int64_t T = WIN_TILE, last = (int64_t(1) << 32) - 1;
@@ -169,6 +225,7 @@ static void test_tiles() {
 int main() {
     test_errors_in_order();
     test_plan();
+    test_adapter_boundary();
     test_tiles();
     if (failures) {
         std::printf("%d checks failed\n", failures);

@@ -1,6 +1,7 @@
-"""The host analysis of the window operator (naive_query_engine_amd/csrc/window_plan.hpp: the argument checks in their order, the
-distinct value columns and their scan operators, the position arrays, the tile and carry counts) on the CPU:
-tests/cpp/test_window_plan.cpp includes that header alone, is compiled with g++ and run."""
+"""The host analysis of the window operator as the first entry sees it (plan_window of naive_query_engine_amd/csrc/window_ex_plan.hpp, the
+adapter onto plan_window_ex: the argument checks in their order, the distinct value columns and their scan operators, the position
+arrays; window_plan.hpp: the tile and carry counts) on the CPU: tests/cpp/test_window_plan.cpp includes window_plan.hpp alone (which
+ends by including the analysis), is compiled with g++ and run."""
 import os
 import subprocess
 

@@ -266,6 +266,33 @@ def test_old_functions_and_frames_are_bit_identical_to_the_old_entry(ctx):
     assert (a.to_numpy().view(np.uint64) == b.to_numpy().view(np.uint64)).all()
 
 
+@pytest.mark.parametrize("n,parts,order", [(5, [0], [1]), (T + 1, [0], [1]), (T + 1, [], [])], ids=["one_tile", "two_tiles_with_carries", "two_tiles_no_keys"])
+def test_both_entries_make_the_same_launches(ctx, n, parts, order):
+    """The old entry is the adapter onto the one body: the same kernels, label for label and launch for launch, as the wider entry over
+    the widened list — the three ranking functions and sum / avg / min over the three frames of one nullable Float64 column."""
+    rng = np.random.default_rng(51)
+    cols = [i64(rng.integers(0, 3, n)), i64(rng.integers(0, max(2, n // 3), n)), Column.from_numpy(rng.normal(0, 10, n), rng.random(n) > 0.2)]
+    old = [(W.RowNumber,), (W.Rank,), (W.DenseRank,)] + [(fn, 2, fr) for fr in wu.FRAMES for fn in (W.Sum, W.Avg, W.Min)]
+    assert len(old) == 12
+    t = ctx.table_from_host(cols)
+
+    def launches(call):
+        with Launches(ctx):
+            out = call()
+            report = {label: count for label, (_, count) in ctx.timing_report().items()}
+        return report, out.to_host()
+
+    a, x = launches(lambda: ctx.window(t, parts, order, old))
+    b, y = launches(lambda: ctx.window_ex(t, parts, order, [wx.old(*f) for f in old]))
+    assert a == b
+    # and they are the launches of such a list: one value column gathered and scanned once, one emit, carries only past one tile, a sort only with keys
+    assert a["win_bounds"] == 1 and a["win_gather"] == 1 and a["win_scan_apply"] == 1 and a["win_pos_apply"] == 1 and a["win_emit"] == 1 and not set(a) & set(NEW_LABELS)
+    assert [a.get(s, 0) for s in ("win_pos_reduce", "win_pos_carry", "win_scan_reduce", "win_scan_carry")] == [int(n > T)] * 4
+    assert any(not s.startswith("win_") for s in a) == bool(parts or order)  # (the sort's kernels are the only ones that are not the unit's own)
+    for f, p, q in zip(old, x, y):
+        assert p.dtype == q.dtype and q.validity is None and (p.to_numpy().view(np.uint64) == q.to_numpy().view(np.uint64)).all(), f
+
+
 # ----------------------------------------------------------------------------- sharing, by launch counts
 def test_scans_are_shared_by_column_and_width(ctx):
     n = 2 * T + 3

@@ -100,8 +100,19 @@ def test_window_spec_ex_binding_matches_the_header_struct():
 def test_the_new_entry_lives_in_the_window_unit():
     unit = open(os.path.join(CSRC, "window.hip")).read()
     code = "\n".join(line.split("//")[0] for line in unit.splitlines())
-    assert "NQE_MODULE_PROBE" not in code and "nqe_status nqe_window_execute_ex(" in code
-    assert code.count("win_order(") == 3 and code.count("win_emit_old(") == 3  # one definition, both entries call it: the body is shared, not copied
+    assert "NQE_MODULE_PROBE" not in code
+    # one body: both entries are defined here and each calls win_execute (its definition is the third mention) ...
+    assert code.count("nqe_status nqe_window_execute(") == 1 and code.count("nqe_status nqe_window_execute_ex(") == 1 and code.count("win_execute(") == 3
+    for entry in ("nqe_status nqe_window_execute(", "nqe_status nqe_window_execute_ex("):
+        body = code[code.index(entry):].split("NQE_API_END()")[0]
+        assert body.count("win_execute(") == 1 and "launch(" not in body and "make_word_column" not in body and "n == 0" not in body, entry
+    assert code.count("plan_window(") == 1 and code.count("plan_window_ex(") == 1 and code.count("win_widen(") == 1  # (both defined in window_ex_plan.hpp)
+    # ... and in it every stage function is defined once and called from one place, every emit launched from one place
+    for stage in ("win_order(", "win_partition_states(", "win_emit_old("):
+        assert code.count(stage) == 2, stage
+        assert code[code.index("win_execute("):].count(stage) == 1, stage  # the call is win_execute's
+    for label in ('"win_emit"', '"win_frame_emit"', '"win_value_emit"'):
+        assert code.count("launch(ctx, " + label) == 1 and code.count(label) == 1, label
     make = open(os.path.join(CSRC, "Makefile")).read()
     assert re.search(r"^window\.o:.*\bwindow_ex_kernels\.hpp\b.*\bwindow_ex_plan\.hpp\b", make, flags=re.M) and "window_ex" not in re.search(r"^SRCS := .*$", make, flags=re.M).group(0)
     plan = open(os.path.join(CSRC, "window_ex_plan.hpp")).read()
@@ -140,6 +151,83 @@ def test_mirror_construction_schema_children():
         with pytest.raises(ErrorCode) as e:
             pp.PhysicalWindowPlanEx.create(scan, [], [], [X(WX.Lag, col("pay"), default=bad)]).schema()
         assert e.value.status == Status.IntervalError
+
+
+class _StubTable:
+    """a device table as a stub context sees it: its context and its column count"""
+
+    def __init__(self, ctx, num_columns):
+        self.ctx, self.num_columns = ctx, num_columns
+
+
+class _StubContext:
+    """the Context methods a window plan calls, recorded in `calls`; nothing is computed"""
+
+    def __init__(self):
+        self.calls = []
+
+    def _table(self, name, num_columns, *args):
+        self.calls.append((name,) + args)
+        return _StubTable(self, num_columns)
+
+    def expr_evaluate(self, table, nodes):
+        return self._table("expr_evaluate", 1, table.num_columns)
+
+    def append_columns(self, table, extra):
+        return self._table("append_columns", table.num_columns + sum(t.num_columns for t in extra))
+
+    def project(self, table, cols):
+        return self._table("project", len(cols))
+
+    def window(self, table, partition_by, order_by, funcs):
+        return self._table("window", len(funcs), table.num_columns, partition_by, order_by, funcs)
+
+    def window_ex(self, table, partition_by, order_by, funcs):
+        return self._table("window_ex", len(funcs), table.num_columns, partition_by, order_by, funcs)
+
+
+class _StubInput(pp.PhysicalPlan):
+    """one batch of EMP's shape on a stub context"""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+
+    def schema(self):
+        return EMP
+
+    def children(self):
+        return []
+
+    def execute(self):
+        return [pp.DeviceRecordBatch(EMP, _StubTable(self.ctx, len(EMP)))]
+
+
+def test_each_plan_reaches_its_own_entry_through_the_shared_body():
+    key = PhysicalBinaryExpr.create(col("department_id"), Operator.Plus, PhysicalLiteralExpr.create(ScalarValue.Int64(1)))
+    arg = PhysicalBinaryExpr.create(col("pay"), Operator.Multiply, PhysicalLiteralExpr.create(ScalarValue.Float64(2.0)))
+    order = [pp.PhysicalSortExpr(col("name"), descending=True, nulls_first=False)]
+    n = len(EMP)
+    cases = (("window", pp.PhysicalWindowPlan, [pp.WindowFunction(W.Sum, arg, F.Rows), pp.WindowFunction(W.Rank), pp.WindowFunction(W.Max, col("id"))]),
+             ("window_ex", pp.PhysicalWindowPlanEx, [pp.WindowFunctionEx(WX.Sum, arg, FX.Rows), pp.WindowFunctionEx(WX.Rank), pp.WindowFunctionEx(WX.Lag, col("id"), offset=3)]))
+    for entry, plan_type, funcs in cases:
+        ctx = _StubContext()
+        (batch,) = plan_type.create(_StubInput(ctx), [key], order, funcs).execute()
+        made = [c for c in ctx.calls if c[0] in ("window", "window_ex")]
+        assert [c[0] for c in made] == [entry]  # its own entry, once, and not the other
+        _, width, parts, keys, specs = made[0]
+        # the key and the argument are temporary columns behind the input's: the call sees them, the batch that leaves does not
+        assert width == n + 2 and parts == [n] and keys == [(1, True, False)]
+        assert batch.table.num_columns == n + len(funcs) and [f.name for f in batch.fields] == [f.name for f in plan_type.create(_StubInput(ctx), [key], order, funcs).schema()]
+        assert [c[0] for c in ctx.calls].count("expr_evaluate") == 2
+        if entry == "window":  # how a function turns into a spec is the other difference
+            assert specs == [(W.Sum, n + 1, F.Rows), (W.Rank, None, F.Range), (W.Max, 0, F.Range)]
+        else:
+            assert specs == [funcs[0].spec(n + 1), funcs[1].spec(None), funcs[2].spec(0)] and specs[2]["param"] == 3
+    # a default of another dtype is refused before anything runs
+    ctx = _StubContext()
+    with pytest.raises(ErrorCode) as e:
+        pp.PhysicalWindowPlanEx.create(_StubInput(ctx), [key], order, [pp.WindowFunctionEx(WX.Lag, col("pay"), default=ScalarValue.Int64(1))]).execute()
+    assert e.value.status == Status.IntervalError and ctx.calls == []
 
 
 def test_rewrite_keeps_the_node_and_rewrites_its_input():
