@@ -28,11 +28,15 @@
 //   build_sorted         (duplicate keys, or an empty build side): perm, slots/cap/shift, direct = no duplicates after all;
 //                        build_sorted_dense adds dense (+ ustart, or the payload fields above when unique); sorted_cols for
 //                        duplicates → probe_duplicates (direct: probe_unique / probe_dense_payload as above)
+// probe_duplicates and the outer probe (probe_outer, quirk Q19, over every build form) are the two entries of ONE count → scan →
+// expand-and-write path, probe_expand: its column list is hash_join_expand_plan.hpp's (plain C++), its kernels one body per pass
+// (expand_count / expand_write in hash_join_probe_kernels.hpp; the outer entries' wrappers in hash_join_outer_kernels.hpp).
 // (the semi / anti probe, quirk Q22, reads the same fields for existence alone: its map from build form to existence form is at probe_semi)
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 
+#include "hash_join_expand_plan.hpp"
 #include "hash_join_semi_kernels.hpp" // (and through it hash_join_outer_kernels.hpp, hash_join_probe_kernels.hpp, hash_join_build_kernels.hpp, hash_join_table.hpp)
 
 // which build rows have matched so far (quirk Q19): bit `start` per matched key, left_rows bits in 32-bit words, bound to one join table
@@ -858,68 +862,104 @@ std::unique_ptr<nqe_table> probe_unique(nqe_ctx *ctx, const nqe_join_table *jt, 
     return out;
 }
 
-// ---- duplicate build keys: count pass, scan, output-driven write pass (probe_count_kernel / probe_write_kernel)
+// the probe key as the lookups take it: a Utf8 key re-encoded through the build side's dictionary (into `codes`), else the column itself
+const DevColumn &encoded_probe_key(nqe_ctx *ctx, const nqe_join_table *jt, const DevColumn &rk_orig, DevColumn &codes) {
+    if (rk_orig.dtype != NQE_UTF8) return rk_orig;
+    codes = utf8_encode_probe(ctx, rk_orig, jt->dict);
+    return codes;
+}
+
+// ---- the expand path: count pass (expand_count), scan, output-driven write pass (expand_write) — ONE path with two entries.
+//   probe_duplicates: the inner probe of a duplicate-key table (probe_count_kernel / probe_write_kernel, labels join_probe_*);
+//   probe_outer:      the outer joins (quirk Q19: HashJoin honouring join_type; outer_count_kernel / outer_write_kernel, labels
+//                     join_outer_*), over EVERY build form — lookup_of(jt) is complete for all of them (`dense` or `slots` is always
+//                     filled) — taking none of the fused one-pass tiers; the build-preserving side adds a pass over the build rows
+//                     (unmatched_build).  The match relation is the inner join's, Q11 included.
+// Which kernel column reads what and lands where is hash_join_expand_plan.hpp's list (plain C++, tested on the CPU for both entries).
+struct ExpandMode {
+    bool null_extend;  // the outer entry: NULL-extended rows, exact null counts
+    bool keep_probe;   // … whose unmatched probe rows stay
+    uint32_t *marks;   // … the bitmap of nqe_join_marks (bit `start` per matched key), or null
+    const char *count_label, *write_label;
+};
 // pass 2 and what follows it: allocates the destination of every kernel column, writes, packs the byte-staged Boolean values and
-// validity, places the columns (out_slot: output column index, -1 outer_pos, -2 inner_pos) and takes the Utf8 columns
-void write_duplicate_matches(nqe_ctx *ctx, const nqe_join_table *jt, const nqe_table *right, int64_t M, const BufRef &pmeta, const BufRef &offs, int grid,
-                             const std::vector<const DevColumn *> &srcs, const std::vector<int> &out_slot, JoinCols &jc, nqe_table *out) {
+// validity, places the columns and takes the Utf8 columns
+void write_matches(nqe_ctx *ctx, const nqe_join_table *jt, const nqe_table *right, const ExpandMode &mode, bool has_null, int64_t M, const BufRef &pmeta, const BufRef &offs,
+                   int grid, const jx::ExpandPlan &plan, const std::vector<DevColumn> &srcs, nqe_table *out) {
     const int64_t n = right->rows;
-    const size_t nleft = jt->left_cols.size();
+    const size_t nleft = jt->left_cols.size(), ncols = plan.cols.size();
+    ExpandCols ec;
+    std::memset(&ec, 0, sizeof(ec));
+    ec.n = int(ncols);
+    ec.n_left = plan.n_left;
+    ec.need_perm = plan.need_perm ? 1 : 0;
     DevColumn outer_pos, inner_pos;
     out->cols.resize(nleft + right->cols.size());
-    std::vector<BufRef> bool_bytes(srcs.size()), valid_bytes(srcs.size());
-    std::vector<DevColumn> dsts(srcs.size());
-    for (size_t k = 0; k < srcs.size(); ++k) {
-        const DevColumn &src = *srcs[k];
-        const bool v = src.validity != nullptr;
-        DevColumn dst = src.dtype == NQE_BOOLEAN ? make_bool_column(ctx, M, v) : make_word_column(ctx, src.dtype, M, v);
-        jc.src[k] = src.values ? src.values->ptr : nullptr;
-        jc.src_valid[k] = src.valid();
-        jc.dtype[k] = src.dtype;
+    std::vector<BufRef> bool_bytes(ncols), valid_bytes(ncols);
+    std::vector<DevColumn> dsts(ncols);
+    for (size_t k = 0; k < ncols; ++k) {
+        const jx::ExpandCol &pc = plan.cols[k];
+        const DevColumn &src = srcs[k];
+        DevColumn dst = src.dtype == NQE_BOOLEAN ? make_bool_column(ctx, M, pc.validity) : make_word_column(ctx, src.dtype, M, pc.validity);
+        ec.by_pos[k] = pc.by_pos ? 1 : 0;
+        ec.from_probe[k] = pc.from_probe ? 1 : 0;
+        ec.src[k] = src.values ? src.values->ptr : nullptr;
+        ec.src_valid[k] = src.valid();
+        ec.dtype[k] = src.dtype;
+        ec.null_word[k] = pc.null_word;
         if (src.dtype == NQE_BOOLEAN) {
             bool_bytes[k] = dev_alloc(ctx, size_t(M) + 8);
-            jc.dst_bool_bytes[k] = (uint8_t *)bool_bytes[k]->ptr;
+            ec.dst_bool_bytes[k] = (uint8_t *)bool_bytes[k]->ptr;
         } else {
-            jc.dst_words[k] = (uint64_t *)dst.values->ptr;
+            ec.dst_words[k] = (uint64_t *)dst.values->ptr;
         }
-        if (v) {
+        if (pc.validity) {
             valid_bytes[k] = dev_alloc(ctx, size_t(M) + 8);
-            jc.dst_valid_bytes[k] = (uint8_t *)valid_bytes[k]->ptr;
+            ec.dst_valid_bytes[k] = (uint8_t *)valid_bytes[k]->ptr;
         }
         dsts[k] = std::move(dst);
     }
-    bool all_plain = true;
-    for (size_t k = 0; k < srcs.size(); ++k)
-        all_plain = all_plain && is_plain_word(*srcs[k]) && jc.dst_words[k] && !jc.dst_bool_bytes[k] && !jc.dst_valid_bytes[k] && srcs[k]->length > 0;
-    if (n && M)
-        launch(ctx, "join_probe_write", all_plain ? probe_write_kernel<true> : probe_write_kernel<false>, dim3(grid), dim3(JT_BLOCK), 0, (const uint64_t *)pmeta->ptr, n,
-               (const uint64_t *)offs->ptr, (const uint32_t *)jt->perm->ptr, jt->direct ? 1 : 0, jc);
-    for (size_t k = 0; k < srcs.size(); ++k) {
+    if (n && M) {
+        auto k = mode.null_extend ? (plan.plain ? outer_write_kernel<true> : outer_write_kernel<false>) : (plan.plain ? probe_write_kernel<true> : probe_write_kernel<false>);
+        launch(ctx, mode.write_label, k, dim3(grid), dim3(JT_BLOCK), 0, (const uint64_t *)pmeta->ptr, n, (const uint64_t *)offs->ptr,
+               jt->perm ? (const uint32_t *)jt->perm->ptr : (const uint32_t *)nullptr, jt->direct ? 1 : 0, ec);
+    }
+    for (size_t k = 0; k < ncols; ++k) {
+        const int slot = plan.cols[k].out_slot;
         if (bool_bytes[k]) pack_bytes_to_bits(ctx, (const uint8_t *)bool_bytes[k]->ptr, M, (uint64_t *)dsts[k].values->ptr);
         if (valid_bytes[k]) pack_bytes_to_bits(ctx, (const uint8_t *)valid_bytes[k]->ptr, M, (uint64_t *)dsts[k].validity->ptr);
-        if (out_slot[k] >= 0) out->cols[size_t(out_slot[k])] = dsts[k];
-        else if (out_slot[k] == -1) outer_pos = dsts[k];
+        if (slot >= 0) out->cols[size_t(slot)] = dsts[k];
+        else if (slot == jx::SLOT_OUTER_POS) outer_pos = dsts[k];
         else inner_pos = dsts[k];
     }
     for (size_t c = 0; c < nleft; ++c)
-        if (jt->left_cols[c].dtype == NQE_UTF8)
-            out->cols[c] = take_utf8(ctx, jt->left_cols[c], (const int64_t *)outer_pos.words(), M, false);
+        if (jt->left_cols[c].dtype == NQE_UTF8) out->cols[c] = take_utf8(ctx, jt->left_cols[c], (const int64_t *)outer_pos.words(), M, has_null);
     for (size_t c = 0; c < right->cols.size(); ++c)
-        if (right->cols[c].dtype == NQE_UTF8)
-            out->cols[nleft + c] = take_utf8(ctx, right->cols[c], (const int64_t *)inner_pos.words(), M, false);
+        if (right->cols[c].dtype == NQE_UTF8) out->cols[nleft + c] = take_utf8(ctx, right->cols[c], (const int64_t *)inner_pos.words(), M, false);
+    if (mode.null_extend) count_nulls_exact(ctx, out);
 }
-std::unique_ptr<nqe_table> probe_duplicates(nqe_ctx *ctx, const nqe_join_table *jt, const nqe_table *right, int right_key, const DevColumn &rk, const DevColumn &rk_orig) {
+// `rk`: the probe key as the lookups take it (encoded_probe_key), `rk_orig`: the caller's column
+std::unique_ptr<nqe_table> probe_expand(nqe_ctx *ctx, const nqe_join_table *jt, const nqe_table *right, int right_key, const DevColumn &rk, const DevColumn &rk_orig,
+                                        const ExpandMode &mode) {
     const int64_t n = right->rows;
     const int64_t ntiles = (n + JT_ROWS - 1) / JT_ROWS;
     BufRef pmeta = dev_alloc(ctx, size_t(n) * 8 + 8);
     BufRef counts = dev_alloc(ctx, size_t(ntiles + 1) * 4);
     BufRef offs = dev_alloc(ctx, size_t(ntiles + 1) * 8);
-    int grid = int(std::max<int64_t>(1, std::min<int64_t>(ntiles, int64_t(ctx->num_cus) * 8)));
-    if (n)
-        launch(ctx, "join_probe_count", probe_count_kernel, dim3(grid), dim3(JT_BLOCK), 0, rk.words(), n, lookup_of(jt), (uint64_t *)pmeta->ptr,
-               (uint32_t *)counts->ptr, ctx->d_flags);
+    BufRef misses;
+    if (mode.null_extend) misses = dev_alloc_zero(ctx, 8);
+    const int grid = int(std::max<int64_t>(1, std::min<int64_t>(ntiles, int64_t(ctx->num_cus) * 8)));
+    if (n && !mode.null_extend) {
+        launch(ctx, mode.count_label, probe_count_kernel, dim3(grid), dim3(JT_BLOCK), 0, rk.words(), n, lookup_of(jt), (uint64_t *)pmeta->ptr, (uint32_t *)counts->ptr, ctx->d_flags);
+    } else if (n) {
+        auto k = mode.keep_probe ? (mode.marks ? outer_count_kernel<true, true> : outer_count_kernel<true, false>)
+                                 : (mode.marks ? outer_count_kernel<false, true> : outer_count_kernel<false, false>);
+        launch(ctx, mode.count_label, k, dim3(grid), dim3(JT_BLOCK), 0, rk.words(), n, lookup_of(jt), (uint64_t *)pmeta->ptr, (uint32_t *)counts->ptr, mode.marks,
+               (unsigned long long *)misses->ptr, ctx->d_flags);
+    }
     exclusive_scan_u32_to_u64(ctx, (const uint32_t *)counts->ptr, (uint64_t *)offs->ptr, ntiles);
     const int64_t M = int64_t(read_scalar(ctx, (const uint64_t *)offs->ptr + ntiles));
+    const bool has_null = mode.keep_probe && read_scalar(ctx, (const unsigned long long *)misses->ptr) != 0ull;
     {
         int f[NQE_NUM_FLAGS];
         flags_read(ctx, f);
@@ -928,61 +968,74 @@ std::unique_ptr<nqe_table> probe_duplicates(nqe_ctx *ctx, const nqe_join_table *
     auto out = std::make_unique<nqe_table>();
     out->ctx = ctx;
     out->rows = M;
-    // the kernel's columns: left columns (Utf8 payload: a row-number column instead — the kernel emits outer_pos / inner_pos, then
-    // the Utf8 `take`), the build key taken from the probe side, right columns
-    bool utf8_left = false, utf8_right = false;
-    for (auto &c : jt->left_cols) utf8_left |= c.dtype == NQE_UTF8;
-    for (auto &c : right->cols) utf8_right |= c.dtype == NQE_UTF8;
-    JoinCols jc;
-    std::memset(&jc, 0, sizeof(jc));
-    DevColumn left_rowid, right_rowid, key_from_probe;
-    std::vector<const DevColumn *> srcs;
-    std::vector<int> out_slot;
-    const bool key_shortcut = jt->key_dtype != NQE_UTF8 && !jt->left_cols[size_t(jt->left_key)].validity;
-    for (size_t c = 0; c < jt->left_cols.size(); ++c)
-        if (jt->left_cols[c].dtype != NQE_UTF8 && !(key_shortcut && int(c) == jt->left_key)) { srcs.push_back(&jt->left_cols[c]); out_slot.push_back(int(c)); }
-    if (utf8_left) {
-        left_rowid = rowid_column(ctx, jt->left_rows);
-        srcs.push_back(&left_rowid); out_slot.push_back(-1);
+    // the kernel's columns.  A Utf8 column goes through a row-number column (the kernel emits outer_pos / inner_pos) and the Utf8
+    // `take`; a plain integer build key is taken from the probe side (the key of a match is bit-identical on both sides), and where
+    // that makes the two key columns of the output identical they are ONE buffer, as in the unique-key forms: a column less to write
+    const DevColumn &lk = jt->left_cols[size_t(jt->left_key)];
+    jx::ExpandSides sides;
+    for (size_t c = 0; c < jt->left_cols.size(); ++c) {
+        jx::SideCol sc;
+        sc.dtype = jt->left_cols[c].dtype;
+        sc.validity = jt->left_cols[c].validity != nullptr;
+        sc.sorted_copy = c < jt->sorted_cols.size() && jt->sorted_cols[c] != nullptr;
+        sides.left.push_back(sc);
     }
-    jc.n_left = int(srcs.size());
-    // … and when equal keys are identical bits the two key columns of the output are ONE buffer (as in the unique-key forms): a
-    // column less to write
-    const bool key_shared = key_shortcut && share_key_column(jt->left_cols[size_t(jt->left_key)], rk_orig);
-    if (key_shortcut && !key_shared) {
-        key_from_probe = as_build_key(rk);
-        srcs.push_back(&key_from_probe); out_slot.push_back(jt->left_key);
+    for (auto &c : right->cols) {
+        jx::SideCol sc;
+        sc.dtype = c.dtype;
+        sc.validity = c.validity != nullptr;
+        sides.right.push_back(sc);
     }
-    for (size_t c = 0; c < right->cols.size(); ++c)
-        if (right->cols[c].dtype != NQE_UTF8) { srcs.push_back(&right->cols[c]); out_slot.push_back(int(jt->left_cols.size() + c)); }
-    if (utf8_right) {
-        right_rowid = rowid_column(ctx, n);
-        srcs.push_back(&right_rowid); out_slot.push_back(-2);
+    sides.left_key = jt->left_key;
+    sides.right_key = right_key;
+    sides.left_rows = jt->left_rows;
+    sides.right_rows = n;
+    sides.direct = jt->direct;
+    sides.keys_shareable = share_key_column(lk, rk_orig);
+    sides.null_extend = mode.null_extend;
+    sides.has_null = has_null;
+    const jx::ExpandPlan plan = jx::plan_expand(sides);
+    if (plan.cols.size() > size_t(MAX_JOIN_COLS)) fail(NQE_ERR_NOT_SUPPORTED, "join output wider than 32 columns");
+    std::vector<DevColumn> srcs(plan.cols.size());
+    for (size_t k = 0; k < plan.cols.size(); ++k) {
+        const jx::ExpandCol &pc = plan.cols[k];
+        DevColumn &s = srcs[k];
+        if (pc.source == jx::SRC_LEFT) {
+            s = jt->left_cols[size_t(pc.index)];
+            if (pc.by_pos) s.values = jt->sorted_cols[size_t(pc.index)];
+        } else if (pc.source == jx::SRC_RIGHT) {
+            s = right->cols[size_t(pc.index)];
+        } else if (pc.source == jx::SRC_PROBE_KEY) {
+            s = as_build_key(rk);
+            s.dtype = pc.dtype;
+        } else {
+            s = rowid_column(ctx, pc.source == jx::SRC_LEFT_ROWID ? jt->left_rows : n);
+        }
     }
-    jc.n = int(srcs.size());
-    if (jc.n > MAX_JOIN_COLS) fail(NQE_ERR_NOT_SUPPORTED, "join output wider than 32 columns");
-    // left columns with a copy in sorted-row order are read at start + match number: the matches of a probe row are adjacent words
-    std::vector<DevColumn> by_pos_cols(size_t(jc.n_left));
-    for (int k = 0; k < jc.n_left; ++k) {
-        const int ci = out_slot[size_t(k)];
-        if (!jt->direct && ci >= 0 && size_t(ci) < jt->sorted_cols.size() && jt->sorted_cols[size_t(ci)]) {
-            by_pos_cols[size_t(k)] = *srcs[size_t(k)];
-            by_pos_cols[size_t(k)].values = jt->sorted_cols[size_t(ci)];
-            srcs[size_t(k)] = &by_pos_cols[size_t(k)];
-            jc.by_pos[k] = 1;
-        } else
-            jc.need_perm = 1;
+    write_matches(ctx, jt, right, mode, has_null, M, pmeta, offs, grid, plan, srcs, out.get());
+    if (plan.key_shared) {
+        out->cols[size_t(jt->left_key)] = out->cols[jt->left_cols.size() + size_t(right_key)];
+        out->cols[size_t(jt->left_key)].dtype = lk.dtype;
     }
-    write_duplicate_matches(ctx, jt, right, M, pmeta, offs, grid, srcs, out_slot, jc, out.get());
-    if (key_shared) out->cols[size_t(jt->left_key)] = out->cols[jt->left_cols.size() + size_t(right_key)];
-    sync(ctx); // temporaries above are released on return; keep the stream drained for simplicity
+    sync(ctx); // the temporaries above are released on return; keep the stream drained for simplicity
     return out;
 }
+// the inner entry: duplicate build keys (probe_table has checked the arguments)
+std::unique_ptr<nqe_table> probe_duplicates(nqe_ctx *ctx, const nqe_join_table *jt, const nqe_table *right, int right_key, const DevColumn &rk, const DevColumn &rk_orig) {
+    return probe_expand(ctx, jt, right, right_key, rk, rk_orig, ExpandMode{false, false, nullptr, "join_probe_count", "join_probe_write"});
+}
+// the outer entry.  `marks`: the bitmap of nqe_join_marks, or null
+std::unique_ptr<nqe_table> probe_outer(nqe_ctx *ctx, const nqe_join_table *jt, const nqe_table *right, int right_key, bool keep_probe, uint32_t *marks) {
+    if (right_key < 0 || size_t(right_key) >= right->cols.size()) fail(NQE_ERR_LOGICAL, "ColumnExpr must has name or idx");
+    const DevColumn &rk_orig = right->cols[size_t(right_key)];
+    check_key_types(jt->key_dtype, rk_orig.dtype);
+    if (jt->left_cols.size() + right->cols.size() > size_t(MAX_JOIN_COLS)) fail(NQE_ERR_NOT_SUPPORTED, "join output wider than 32 columns");
+    if (keep_probe && jt->left_rows > int64_t(OUTER_NULL_START)) fail(NQE_ERR_NOT_SUPPORTED, "outer join: a build side of 2^32 rows collides with the no-match mark");
+    DevColumn rk_codes;
+    const DevColumn &rk = encoded_probe_key(ctx, jt, rk_orig, rk_codes);
+    return probe_expand(ctx, jt, right, right_key, rk, rk_orig, ExpandMode{true, keep_probe, marks, "join_outer_count", "join_outer_write"});
+}
 
-// ---- outer joins (quirk Q19): HashJoin honouring join_type.  ONE general path over every build form — lookup_of(jt) is complete for
-// all of them (`dense` or `slots` is always filled) — that takes none of the fused one-pass tiers: count pass (outer_count_kernel),
-// scan, output-driven write pass (outer_write_kernel), and for the build-preserving side a pass over the build rows
-// (unmatched_build_kernel) + compaction.  The match relation is the inner join's, Q11 included.
 // exact null counts of the nullable columns of `out` (count_set_bits_kernel per column, one read-back for all of them); declared in
 // nqe_internal.hpp (set_ops.hip calls it too): true when it waited for the stream
 } // namespace
@@ -1006,147 +1059,6 @@ bool count_nulls_exact(nqe_ctx *ctx, nqe_table *out, const char *label) {
     return true;
 }
 namespace {
-// pass 2 of the outer probe and what follows it (cf. write_duplicate_matches): a left column gets a validity buffer when its source
-// has one or the batch holds a NULL-extended row (`has_null`)
-void write_outer_matches(nqe_ctx *ctx, const nqe_join_table *jt, const nqe_table *right, int64_t M, bool has_null, const BufRef &pmeta, const BufRef &offs, int grid,
-                         const std::vector<const DevColumn *> &srcs, const std::vector<int> &out_slot, OuterCols &oc, nqe_table *out) {
-    const int64_t n = right->rows;
-    const size_t nleft = jt->left_cols.size();
-    DevColumn outer_pos, inner_pos;
-    out->cols.resize(nleft + right->cols.size());
-    std::vector<BufRef> bool_bytes(srcs.size()), valid_bytes(srcs.size());
-    std::vector<DevColumn> dsts(srcs.size());
-    bool all_plain = true;
-    for (size_t k = 0; k < srcs.size(); ++k) {
-        const DevColumn &src = *srcs[k];
-        const bool left = int(k) < oc.n_left;
-        const bool rowid = out_slot[k] < 0; // outer_pos / inner_pos: the NULL of a take index is -1, not a validity bit
-        const bool v = src.validity != nullptr || (left && has_null && !rowid);
-        DevColumn dst = src.dtype == NQE_BOOLEAN ? make_bool_column(ctx, M, v) : make_word_column(ctx, src.dtype, M, v);
-        oc.src[k] = src.values ? src.values->ptr : nullptr;
-        oc.src_valid[k] = src.valid();
-        oc.dtype[k] = src.dtype;
-        oc.null_word[k] = rowid ? ~0ull : 0ull;
-        if (src.dtype == NQE_BOOLEAN) {
-            bool_bytes[k] = dev_alloc(ctx, size_t(M) + 8);
-            oc.dst_bool_bytes[k] = (uint8_t *)bool_bytes[k]->ptr;
-        } else {
-            oc.dst_words[k] = (uint64_t *)dst.values->ptr;
-        }
-        if (v) {
-            valid_bytes[k] = dev_alloc(ctx, size_t(M) + 8);
-            oc.dst_valid_bytes[k] = (uint8_t *)valid_bytes[k]->ptr;
-        }
-        all_plain = all_plain && is_plain_word(src);
-        dsts[k] = std::move(dst);
-    }
-    if (n && M)
-        launch(ctx, "join_outer_write", all_plain ? outer_write_kernel<true> : outer_write_kernel<false>, dim3(grid), dim3(JT_BLOCK), 0, (const uint64_t *)pmeta->ptr, n,
-               (const uint64_t *)offs->ptr, jt->perm ? (const uint32_t *)jt->perm->ptr : (const uint32_t *)nullptr, jt->direct ? 1 : 0, oc);
-    for (size_t k = 0; k < srcs.size(); ++k) {
-        if (bool_bytes[k]) pack_bytes_to_bits(ctx, (const uint8_t *)bool_bytes[k]->ptr, M, (uint64_t *)dsts[k].values->ptr);
-        if (valid_bytes[k]) pack_bytes_to_bits(ctx, (const uint8_t *)valid_bytes[k]->ptr, M, (uint64_t *)dsts[k].validity->ptr);
-        if (out_slot[k] >= 0) out->cols[size_t(out_slot[k])] = dsts[k];
-        else if (out_slot[k] == -1) outer_pos = dsts[k];
-        else inner_pos = dsts[k];
-    }
-    for (size_t c = 0; c < nleft; ++c)
-        if (jt->left_cols[c].dtype == NQE_UTF8) out->cols[c] = take_utf8(ctx, jt->left_cols[c], (const int64_t *)outer_pos.words(), M, has_null);
-    for (size_t c = 0; c < right->cols.size(); ++c)
-        if (right->cols[c].dtype == NQE_UTF8) out->cols[nleft + c] = take_utf8(ctx, right->cols[c], (const int64_t *)inner_pos.words(), M, false);
-    count_nulls_exact(ctx, out);
-}
-// `marks`: the bitmap of nqe_join_marks (bit `start` per matched key), or null
-std::unique_ptr<nqe_table> probe_outer(nqe_ctx *ctx, const nqe_join_table *jt, const nqe_table *right, int right_key, bool keep_probe, uint32_t *marks) {
-    if (right_key < 0 || size_t(right_key) >= right->cols.size()) fail(NQE_ERR_LOGICAL, "ColumnExpr must has name or idx");
-    const DevColumn &rk_orig = right->cols[size_t(right_key)];
-    check_key_types(jt->key_dtype, rk_orig.dtype);
-    if (jt->left_cols.size() + right->cols.size() > size_t(MAX_JOIN_COLS)) fail(NQE_ERR_NOT_SUPPORTED, "join output wider than 32 columns");
-    if (keep_probe && jt->left_rows > int64_t(OUTER_NULL_START)) fail(NQE_ERR_NOT_SUPPORTED, "outer join: a build side of 2^32 rows collides with the no-match mark");
-    DevColumn rk_codes;
-    if (rk_orig.dtype == NQE_UTF8) rk_codes = utf8_encode_probe(ctx, rk_orig, jt->dict);
-    const DevColumn &rk = rk_orig.dtype == NQE_UTF8 ? rk_codes : rk_orig;
-    const int64_t n = right->rows;
-    const int64_t ntiles = (n + JT_ROWS - 1) / JT_ROWS;
-    BufRef pmeta = dev_alloc(ctx, size_t(n) * 8 + 8);
-    BufRef counts = dev_alloc(ctx, size_t(ntiles + 1) * 4);
-    BufRef offs = dev_alloc(ctx, size_t(ntiles + 1) * 8);
-    BufRef misses = dev_alloc_zero(ctx, 8);
-    const int grid = int(std::max<int64_t>(1, std::min<int64_t>(ntiles, int64_t(ctx->num_cus) * 8)));
-    if (n) {
-        auto k = keep_probe ? (marks ? outer_count_kernel<true, true> : outer_count_kernel<true, false>) : (marks ? outer_count_kernel<false, true> : outer_count_kernel<false, false>);
-        launch(ctx, "join_outer_count", k, dim3(grid), dim3(JT_BLOCK), 0, rk.words(), n, lookup_of(jt), (uint64_t *)pmeta->ptr, (uint32_t *)counts->ptr, marks,
-               (unsigned long long *)misses->ptr, ctx->d_flags);
-    }
-    exclusive_scan_u32_to_u64(ctx, (const uint32_t *)counts->ptr, (uint64_t *)offs->ptr, ntiles);
-    const int64_t M = int64_t(read_scalar(ctx, (const uint64_t *)offs->ptr + ntiles));
-    const bool has_null = keep_probe && read_scalar(ctx, (const unsigned long long *)misses->ptr) != 0ull;
-    {
-        int f[NQE_NUM_FLAGS];
-        flags_read(ctx, f);
-        if (f[NQE_FLAG_TABLE_FULL]) fail(NQE_ERR_OUT_OF_MEMORY, "join output of one probe tile exceeds 2^32 rows");
-    }
-    auto out = std::make_unique<nqe_table>();
-    out->ctx = ctx;
-    out->rows = M;
-    // the kernel's columns: left columns, right columns; a Utf8 column goes through a row-number column (outer_pos / inner_pos) and the
-    // Utf8 `take`.  A plain integer build key is taken from the probe side at the probe row (the key of a match is bit-identical on both
-    // sides; a NULL-extended row gets 0 under a NULL all the same), and in a batch without NULL-extended rows the two key columns of the
-    // output are ONE buffer, as in the inner join
-    bool utf8_left = false, utf8_right = false;
-    for (auto &c : jt->left_cols) utf8_left |= c.dtype == NQE_UTF8;
-    for (auto &c : right->cols) utf8_right |= c.dtype == NQE_UTF8;
-    OuterCols oc;
-    std::memset(&oc, 0, sizeof(oc));
-    DevColumn left_rowid, right_rowid, key_from_probe;
-    std::vector<const DevColumn *> srcs;
-    std::vector<int> out_slot;
-    const bool key_shortcut = jt->key_dtype != NQE_UTF8 && !jt->left_cols[size_t(jt->left_key)].validity;
-    const bool key_shared = key_shortcut && !has_null && share_key_column(jt->left_cols[size_t(jt->left_key)], rk_orig);
-    for (size_t c = 0; c < jt->left_cols.size(); ++c) {
-        if (jt->left_cols[c].dtype == NQE_UTF8 || (key_shared && int(c) == jt->left_key)) continue;
-        if (key_shortcut && int(c) == jt->left_key) {
-            key_from_probe = as_build_key(rk);
-            key_from_probe.dtype = jt->left_cols[c].dtype;
-            oc.from_probe[srcs.size()] = 1;
-            srcs.push_back(&key_from_probe);
-        } else
-            srcs.push_back(&jt->left_cols[c]);
-        out_slot.push_back(int(c));
-    }
-    if (utf8_left) {
-        left_rowid = rowid_column(ctx, jt->left_rows);
-        srcs.push_back(&left_rowid); out_slot.push_back(-1);
-    }
-    oc.n_left = int(srcs.size());
-    for (size_t c = 0; c < right->cols.size(); ++c)
-        if (right->cols[c].dtype != NQE_UTF8) { srcs.push_back(&right->cols[c]); out_slot.push_back(int(jt->left_cols.size() + c)); }
-    if (utf8_right) {
-        right_rowid = rowid_column(ctx, n);
-        srcs.push_back(&right_rowid); out_slot.push_back(-2);
-    }
-    oc.n = int(srcs.size());
-    // left columns with a copy in sorted-row order are read at start + match number (see probe_duplicates)
-    std::vector<DevColumn> by_pos_cols(size_t(oc.n_left));
-    for (int k = 0; k < oc.n_left; ++k) {
-        const int ci = out_slot[size_t(k)];
-        if (oc.from_probe[k]) continue;
-        if (!jt->direct && ci >= 0 && size_t(ci) < jt->sorted_cols.size() && jt->sorted_cols[size_t(ci)]) {
-            by_pos_cols[size_t(k)] = *srcs[size_t(k)];
-            by_pos_cols[size_t(k)].values = jt->sorted_cols[size_t(ci)];
-            srcs[size_t(k)] = &by_pos_cols[size_t(k)];
-            oc.by_pos[k] = 1;
-        } else
-            oc.need_perm = 1;
-    }
-    write_outer_matches(ctx, jt, right, M, has_null, pmeta, offs, grid, srcs, out_slot, oc, out.get());
-    if (key_shared) {
-        out->cols[size_t(jt->left_key)] = out->cols[jt->left_cols.size() + size_t(right_key)];
-        out->cols[size_t(jt->left_key)].dtype = jt->left_cols[size_t(jt->left_key)].dtype;
-    }
-    sync(ctx); // the temporaries above are released on return
-    return out;
-}
 // m rows of NULL: zero words / false bits / zero-length strings under an all-zero validity buffer (none at 0 rows: no NULL-extended row)
 DevColumn null_column(nqe_ctx *ctx, int dtype, int64_t m) {
     DevColumn c;
@@ -1166,29 +1078,34 @@ DevColumn null_column(nqe_ctx *ctx, int dtype, int64_t m) {
     }
     return c;
 }
-// the build rows whose bit is not set, in ascending build row, every right column NULL
-std::unique_ptr<nqe_table> unmatched_build(nqe_ctx *ctx, const nqe_join_table *jt, const uint32_t *marks, const int32_t *right_dtypes, int num_right) {
-    if (jt->left_cols.size() + size_t(num_right) > size_t(MAX_JOIN_COLS)) fail(NQE_ERR_NOT_SUPPORTED, "join output wider than 32 columns");
+// the build rows whose bit is set (anti: not set), in ascending build row: KEEP mask over the build rows (marked_build_kernel) →
+// compaction of the visible left columns.  What else the output holds, and its null counts, are the caller's
+std::unique_ptr<nqe_table> compact_marked_build(nqe_ctx *ctx, const nqe_join_table *jt, const uint32_t *marks, bool anti, const char *label) {
     const int64_t n = jt->left_rows;
     DevColumn codes;
     const uint64_t *bkeys = nullptr;
     if (!jt->direct) { // duplicate keys: the row's own key finds the bit its key group shares
         const DevColumn &kc = jt->left_cols[size_t(jt->left_key)];
-        if (kc.dtype == NQE_UTF8) codes = utf8_encode_probe(ctx, kc, jt->dict);
-        bkeys = kc.dtype == NQE_UTF8 ? codes.words() : kc.words();
+        bkeys = encoded_probe_key(ctx, jt, kc, codes).words();
     }
     BufRef counts;
     KeepMask km = new_keep_mask(ctx, n, &counts);
     if (km.ntiles)
-        launch(ctx, "join_outer_unmatched", unmatched_build_kernel, dim3(stream_grid(ctx, km.ntiles, 4)), dim3(256), 0, bkeys, n, km.ntiles, lookup_of(jt), marks,
+        launch(ctx, label, anti ? marked_build_kernel<true> : marked_build_kernel<false>, dim3(stream_grid(ctx, km.ntiles, 4)), dim3(256), 0, bkeys, n, km.ntiles, lookup_of(jt), marks,
                (uint64_t *)km.keep->ptr, (uint32_t *)counts->ptr);
-    km = finish_mask(ctx, km, counts);
+    km = finish_mask(ctx, km, counts); // (waits for the stream: the codes may go)
     auto out = std::make_unique<nqe_table>();
     out->ctx = ctx;
     out->rows = km.total;
     const size_t visible = jt->left_cols.size() - (jt->keys ? 1 : 0); // (the hidden code column of a join on several keys, the last one, is not gathered)
     for (size_t c = 0; c < visible; ++c) out->cols.push_back(compact_column(ctx, jt->left_cols[c], km));
-    for (int k = 0; k < num_right; ++k) out->cols.push_back(null_column(ctx, right_dtypes[k], km.total));
+    return out;
+}
+// the outer joins' build-preserving side: the build rows whose bit is not set, every right column NULL
+std::unique_ptr<nqe_table> unmatched_build(nqe_ctx *ctx, const nqe_join_table *jt, const uint32_t *marks, const int32_t *right_dtypes, int num_right) {
+    if (jt->left_cols.size() + size_t(num_right) > size_t(MAX_JOIN_COLS)) fail(NQE_ERR_NOT_SUPPORTED, "join output wider than 32 columns");
+    auto out = compact_marked_build(ctx, jt, marks, true, "join_outer_unmatched");
+    for (int k = 0; k < num_right; ++k) out->cols.push_back(null_column(ctx, right_dtypes[k], out->rows));
     count_nulls_exact(ctx, out.get());
     sync(ctx);
     return out;
@@ -1224,10 +1141,8 @@ template <int TABLE, bool NULLS, bool MARKS> void launch_semi_coop(nqe_ctx *ctx,
 // (null otherwise).  Returns null for the mark-only pass (`want_out` false).
 std::unique_ptr<nqe_table> probe_semi(nqe_ctx *ctx, const nqe_join_table *jt, const nqe_table *right_with_key, size_t out_cols, bool anti, const SemiValid *key_valid,
                                       uint32_t *marks, bool want_out) {
-    const DevColumn &rk_orig = right_with_key->cols.back();
     DevColumn rk_codes;
-    if (rk_orig.dtype == NQE_UTF8) rk_codes = utf8_encode_probe(ctx, rk_orig, jt->dict);
-    const DevColumn &rk = rk_orig.dtype == NQE_UTF8 ? rk_codes : rk_orig;
+    const DevColumn &rk = encoded_probe_key(ctx, jt, right_with_key->cols.back(), rk_codes);
     const int64_t n = right_with_key->rows;
     BufRef counts;
     KeepMask km;
@@ -1293,27 +1208,9 @@ std::unique_ptr<nqe_table> probe_semi(nqe_ctx *ctx, const nqe_join_table *jt, co
     sync(ctx);
     return out;
 }
-// the build rows whose bit is set (anti: not set), in ascending build row: the visible left columns and nothing else
+// the semi / anti joins' build side: the visible left columns and nothing else
 std::unique_ptr<nqe_table> marked_build(nqe_ctx *ctx, const nqe_join_table *jt, const uint32_t *marks, bool anti) {
-    const int64_t n = jt->left_rows;
-    DevColumn codes;
-    const uint64_t *bkeys = nullptr;
-    if (!jt->direct) { // duplicate keys: the row's own key finds the bit its key group shares
-        const DevColumn &kc = jt->left_cols[size_t(jt->left_key)];
-        if (kc.dtype == NQE_UTF8) codes = utf8_encode_probe(ctx, kc, jt->dict);
-        bkeys = kc.dtype == NQE_UTF8 ? codes.words() : kc.words();
-    }
-    BufRef counts;
-    KeepMask km = new_keep_mask(ctx, n, &counts);
-    if (km.ntiles)
-        launch(ctx, "join_semi_marked", anti ? marked_build_kernel<true> : marked_build_kernel<false>, dim3(stream_grid(ctx, km.ntiles, 4)), dim3(256), 0, bkeys, n, km.ntiles, lookup_of(jt),
-               marks, (uint64_t *)km.keep->ptr, (uint32_t *)counts->ptr);
-    km = finish_mask(ctx, km, counts);
-    auto out = std::make_unique<nqe_table>();
-    out->ctx = ctx;
-    out->rows = km.total;
-    const size_t visible = jt->left_cols.size() - (jt->keys ? 1 : 0); // (never the hidden code column of a join on several keys)
-    for (size_t c = 0; c < visible; ++c) out->cols.push_back(compact_column(ctx, jt->left_cols[c], km));
+    auto out = compact_marked_build(ctx, jt, marks, anti, "join_semi_marked");
     count_nulls_exact(ctx, out.get(), "join_semi_null_count");
     sync(ctx);
     return out;
@@ -1324,8 +1221,7 @@ std::unique_ptr<nqe_table> probe_table(nqe_ctx *ctx, const nqe_join_table *jt, c
     const DevColumn &rk_orig = right->cols[size_t(right_key)];
     check_key_types(jt->key_dtype, rk_orig.dtype);
     DevColumn rk_codes;
-    if (rk_orig.dtype == NQE_UTF8) rk_codes = utf8_encode_probe(ctx, rk_orig, jt->dict);
-    const DevColumn &rk = rk_orig.dtype == NQE_UTF8 ? rk_codes : rk_orig;
+    const DevColumn &rk = encoded_probe_key(ctx, jt, rk_orig, rk_codes);
     if (jt->left_cols.size() + right->cols.size() > size_t(MAX_JOIN_COLS)) fail(NQE_ERR_NOT_SUPPORTED, "join output wider than 32 columns");
     bool right_plain = true;
     for (auto &c : right->cols) right_plain = right_plain && is_plain_word(c);
@@ -1338,13 +1234,12 @@ std::unique_ptr<nqe_table> probe_table(nqe_ctx *ctx, const nqe_join_table *jt, c
 void refuse_tuple_table(const nqe_join_table *jt, const char *who) {
     if (jt->keys) fail(NQE_ERR_INVALID_ARGUMENT, std::string(who) + ": the join table was built on several keys (nqe_hash_join_probe_keys probes it)");
 }
-void check_outer_args(nqe_ctx *ctx, const nqe_join_table *build, uint32_t flags, const nqe_join_marks *marks) {
-    if (flags & ~NQE_JOIN_KEEP_PROBE) fail(NQE_ERR_INVALID_ARGUMENT, "nqe_hash_join_probe_outer: unknown flag bits");
-    if (marks && (marks->ctx != ctx || marks->table != build || marks->rows != build->left_rows))
-        fail(NQE_ERR_INVALID_ARGUMENT, "nqe_hash_join_probe_outer: the marks belong to another join table or context");
-}
 bool foreign_marks(nqe_ctx *ctx, const nqe_join_table *build, const nqe_join_marks *marks) {
     return marks->ctx != ctx || marks->table != build || marks->rows != build->left_rows;
+}
+void check_outer_args(nqe_ctx *ctx, const nqe_join_table *build, uint32_t flags, const nqe_join_marks *marks) {
+    if (flags & ~NQE_JOIN_KEEP_PROBE) fail(NQE_ERR_INVALID_ARGUMENT, "nqe_hash_join_probe_outer: unknown flag bits");
+    if (marks && foreign_marks(ctx, build, marks)) fail(NQE_ERR_INVALID_ARGUMENT, "nqe_hash_join_probe_outer: the marks belong to another join table or context");
 }
 
 } // namespace
@@ -1444,8 +1339,7 @@ nqe_status nqe_hash_join_unmatched_build(nqe_ctx *ctx, const nqe_join_table *bui
     NQE_API_BEGIN(ctx)
     if (!ctx || !build || !out) fail(NQE_ERR_INVALID_ARGUMENT, "bad arguments");
     if (!marks) fail(NQE_ERR_INVALID_ARGUMENT, "nqe_hash_join_unmatched_build: marks are required");
-    if (marks->ctx != ctx || marks->table != build || marks->rows != build->left_rows)
-        fail(NQE_ERR_INVALID_ARGUMENT, "nqe_hash_join_unmatched_build: the marks belong to another join table or context");
+    if (foreign_marks(ctx, build, marks)) fail(NQE_ERR_INVALID_ARGUMENT, "nqe_hash_join_unmatched_build: the marks belong to another join table or context");
     if (num_right < 0 || (num_right > 0 && !right_dtypes)) fail(NQE_ERR_INVALID_ARGUMENT, "nqe_hash_join_unmatched_build: bad right_dtypes");
     for (int32_t k = 0; k < num_right; ++k) {
         if (right_dtypes[k] < NQE_NULLTYPE || right_dtypes[k] > NQE_UTF8) fail(NQE_ERR_INVALID_ARGUMENT, "nqe_hash_join_unmatched_build: a dtype outside nqe_dtype");

@@ -1,6 +1,7 @@
 // hash_join_probe_kernels.hpp — the device side of the join's probe (included once, by hash_join.hip, after
 // hash_join_build_kernels.hpp: probe_one lives there): the lookups of the unique-key forms, the presence pass and the fused write of
-// the dense-payload form, and the count / write passes of the duplicate-key form.
+// the dense-payload form, and the two passes of the expand path — expand_count / expand_write, the one body each behind the inner
+// entries here (probe_count_kernel, probe_write_kernel: the duplicate-key form) and the outer entries of hash_join_outer_kernels.hpp.
 #pragma once
 #include "hash_join_build_kernels.hpp"
 
@@ -423,10 +424,26 @@ __global__ void __launch_bounds__(256) probe_packed_kernel(const uint64_t *rkeys
     }
 }
 
-// pass 1: one table lookup per probe row; records meta and per-tile totals
-__global__ void __launch_bounds__(JT_BLOCK) probe_count_kernel(const uint64_t *rkeys, int64_t n, Lookup L, uint64_t *pmeta,
-                                                               uint32_t *tile_counts, int *flags) {
+// ---- the count → scan → expand-and-write path (hash_join.hip: probe_expand).  ONE body per pass; its entries are the inner probe of a
+// duplicate-key table (probe_count_kernel, probe_write_kernel) and the outer probe (hash_join_outer_kernels.hpp).
+
+// `start` recorded for a probe row without a match (count 1): build rows and positions in the sorted row list are < 2^32 - 1 —
+// build_table refuses 2^32 rows and more, and the outer probe refuses the one size (2^32 rows) at which the last row would collide
+constexpr uint32_t OUTER_NULL_START = 0xFFFFFFFFu;
+
+// pass 1: one table lookup per probe row; records meta (start << 32 | count) and per-tile totals.  The outer entry's additions:
+// KEEP_PROBE: a miss counts 1 and records OUTER_NULL_START (the write pass emits one row with every left column NULL); the misses
+//             are summed into *misses (one atomic per 4096-row tile that has any): the host decides from it whether the left
+//             columns of this batch get a validity buffer.
+// MARKS:      a hit sets bit `start` of `marks` (direct: the build row; duplicate keys: the key's first position in the sorted row
+//             list — every row of the key shares it).  One atomic per matching probe row, behind a plain read that skips it when
+//             the bit is already set: a foreign key hits each primary key ~100 times, and bits only ever go from 0 to 1 (a stale
+//             0 costs one redundant atomic, nothing else).
+template <bool KEEP_PROBE, bool MARKS>
+__device__ __forceinline__ void expand_count(const uint64_t *rkeys, int64_t n, Lookup L, uint64_t *pmeta, uint32_t *tile_counts, uint32_t *marks,
+                                             unsigned long long *misses, int *flags) {
     __shared__ uint64_t wave_tot[JT_BLOCK / 64];
+    __shared__ uint32_t wave_miss[JT_BLOCK / 64];
     for (int64_t tile = blockIdx.x; tile * JT_ROWS < n; tile += gridDim.x) {
         uint64_t keys[JT_ITERS];
 #pragma unroll
@@ -435,29 +452,51 @@ __global__ void __launch_bounds__(JT_BLOCK) probe_count_kernel(const uint64_t *r
             keys[it] = i < n ? rkeys[i] : 0;
         }
         uint64_t local = 0;
+        uint32_t miss = 0;
 #pragma unroll
         for (int it = 0; it < JT_ITERS; ++it) {
             int64_t i = tile * JT_ROWS + int64_t(it) * JT_BLOCK + threadIdx.x;
             if (i < n) {
                 uint64_t m = lookup_meta(L, keys[it]);
+                if (m != 0ull) {
+                    if (MARKS) {
+                        const uint32_t s = uint32_t(m >> 32), bit = 1u << (s & 31u);
+                        uint32_t *w = marks + (s >> 5);
+                        if (!(*w & bit)) atomicOr(w, bit);
+                    }
+                } else if (KEEP_PROBE) {
+                    m = (uint64_t(OUTER_NULL_START) << 32) | 1ull;
+                    ++miss;
+                }
                 pmeta[i] = m;
                 local += m & 0xFFFFFFFFull;
             }
         }
-        for (int d = 32; d > 0; d >>= 1) local += __shfl_down((unsigned long long)local, d, 64);
-        if (lane_id() == 0) wave_tot[threadIdx.x / 64] = local;
+        for (int d = 32; d > 0; d >>= 1) {
+            local += __shfl_down((unsigned long long)local, d, 64);
+            if (KEEP_PROBE) miss += __shfl_down(miss, d, 64);
+        }
+        if (lane_id() == 0) {
+            wave_tot[threadIdx.x / 64] = local;
+            wave_miss[threadIdx.x / 64] = miss;
+        }
         __syncthreads();
         if (threadIdx.x == 0) {
-            uint64_t t = 0;
-            for (int w = 0; w < JT_BLOCK / 64; ++w) t += wave_tot[w];
+            uint64_t t = 0, tm = 0;
+            for (int w = 0; w < JT_BLOCK / 64; ++w) t += wave_tot[w], tm += wave_miss[w];
             if (t > 0xFFFFFFFFull) {
                 atomicOr(&flags[NQE_FLAG_TABLE_FULL], 1);
                 t = 0;
             }
             tile_counts[tile] = uint32_t(t);
+            if (KEEP_PROBE && tm) atomicAdd(misses, (unsigned long long)tm);
         }
         __syncthreads();
     }
+}
+__global__ void __launch_bounds__(JT_BLOCK) probe_count_kernel(const uint64_t *rkeys, int64_t n, Lookup L, uint64_t *pmeta,
+                                                               uint32_t *tile_counts, int *flags) {
+    expand_count<false, false>(rkeys, n, L, pmeta, tile_counts, nullptr, nullptr, flags);
 }
 
 // pass 2, output-driven ("load-balanced expansion"): a tile of probe rows is scanned in LDS; lane j of the
@@ -467,9 +506,14 @@ __global__ void __launch_bounds__(JT_BLOCK) probe_count_kernel(const uint64_t *r
 // exactly the order of the reference's outer_pos/inner_pos (hash_join.rs:86-101).
 // PLAIN: every source column is a plain 8-byte column without validity written as words (C4 with duplicate build keys: the whole
 // output): no dtype dispatch, validity test or byte-array branches in the per-column loop
-template <bool PLAIN>
-__global__ void __launch_bounds__(JT_BLOCK) probe_write_kernel(const uint64_t *pmeta, int64_t n, const uint64_t *tile_offsets,
-                                                               const uint32_t *perm, int direct, JoinCols jc) {
+// NULL_EXTEND (the outer entry): a probe row whose recorded start is OUTER_NULL_START emits one row whose left columns hold null_word
+// (0) / a false bit and validity byte 0; a left column's validity is source validity AND matched; a from_probe left column is read at
+// the probe row.  Nothing of the build side is read for such a row (the build side may be empty), and on PLAIN a left column may
+// still have a validity byte array (it has one when the batch contains a NULL-extended row).  Without NULL_EXTEND every live row is a
+// hit and all of this folds away: the PLAIN instance loads unconditionally (dead lanes read source row 0 — the host grants PLAIN only
+// when no source is empty) and stores behind live[q] alone.
+template <bool PLAIN, bool NULL_EXTEND>
+__device__ __forceinline__ void expand_write(const uint64_t *pmeta, int64_t n, const uint64_t *tile_offsets, const uint32_t *perm, int direct, const ExpandCols &ec) {
     __shared__ uint32_t off[PW_TILE + 1];
     __shared__ uint32_t startv[PW_TILE];
     __shared__ uint32_t wave_tot[JT_BLOCK / 64];
@@ -508,17 +552,17 @@ __global__ void __launch_bounds__(JT_BLOCK) probe_write_kernel(const uint64_t *p
             __syncthreads();
             // ---- one lane per output row.  The lanes are shifted by the output position's offset inside its 128-byte line, so that every
             // wave's 64 consecutive words are four whole lines (round 5: a non-temporal store of a partial line is the costliest store there is)
-            const int32_t head = int32_t(out_base & 15);
-            for (int32_t j0 = -head; j0 < int32_t(total); j0 += JT_BLOCK * 4) {
+            // (64-bit positions: one sub-tile may expand to 2^31 output rows and more — only the whole tile is bounded, at 2^32)
+            const int64_t head = int64_t(out_base & 15);
+            for (int64_t j0 = -head; j0 < int64_t(total); j0 += JT_BLOCK * 4) {
                 uint32_t prow[4], brow[4], bpos[4];
-                bool live[4];
+                bool live[4], hit[4]; // hit: a live row that has a build row (not NULL-extended)
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    const int32_t js = j0 + q * JT_BLOCK + int32_t(threadIdx.x);
-                    const uint32_t j = uint32_t(js);
-                    live[q] = js >= 0 && js < int32_t(total);
+                    const int64_t js = j0 + q * JT_BLOCK + int64_t(threadIdx.x);
+                    live[q] = js >= 0 && js < int64_t(total);
                     uint32_t lo = 0, hi = PW_TILE; // largest lo with off[lo] <= j
-                    uint32_t jj = live[q] ? j : 0;
+                    const uint32_t jj = live[q] ? uint32_t(js) : 0;
 #pragma unroll
                     for (int step = 0; step < 10; ++step) {
                         uint32_t mid = (lo + hi) >> 1;
@@ -527,37 +571,54 @@ __global__ void __launch_bounds__(JT_BLOCK) probe_write_kernel(const uint64_t *p
                         hi = go ? hi : mid;
                     }
                     prow[q] = lo;
-                    uint32_t mth = jj - off[lo];
-                    bpos[q] = live[q] ? startv[lo] + mth : 0u;
-                    brow[q] = live[q] ? (direct ? startv[lo] : (jc.need_perm ? perm[startv[lo] + mth] : 0u)) : 0u;
+                    const uint32_t st = startv[lo], mth = jj - off[lo];
+                    hit[q] = live[q] && (!NULL_EXTEND || st != OUTER_NULL_START);
+                    bpos[q] = hit[q] ? st + mth : 0u;
+                    brow[q] = hit[q] ? (direct ? st : (ec.need_perm ? perm[st + mth] : 0u)) : 0u;
                 }
-                for (int c = 0; c < jc.n; ++c) {
-                    const bool left = c < jc.n_left;
-                    const void *src = jc.src[c];
+                for (int c = 0; c < ec.n; ++c) {
+                    const bool left = c < ec.n_left;
+                    const void *src = ec.src[c];
+                    const bool by_pos = ec.by_pos[c] != 0, from_probe = NULL_EXTEND && ec.from_probe[c] != 0;
                     if (PLAIN) {
+                        uint8_t *__restrict__ vb = NULL_EXTEND ? ec.dst_valid_bytes[c] : nullptr;
                         const uint64_t *__restrict__ sw = static_cast<const uint64_t *>(src);
-                        uint64_t *__restrict__ dw = jc.dst_words[c];
-                        const bool by_pos = jc.by_pos[c] != 0;
+                        uint64_t *__restrict__ dw = ec.dst_words[c];
+                        const uint64_t nw = NULL_EXTEND ? ec.null_word[c] : 0ull;
                         uint64_t v[4];
 #pragma unroll
-                        for (int q = 0; q < 4; ++q) v[q] = sw[left ? int64_t(by_pos ? bpos[q] : brow[q]) : (live[q] ? row0 + prow[q] : int64_t(0))]; // (dead lanes read row 0)
+                        for (int q = 0; q < 4; ++q) {
+                            if (!NULL_EXTEND) v[q] = sw[left ? int64_t(by_pos ? bpos[q] : brow[q]) : (live[q] ? row0 + prow[q] : int64_t(0))]; // (dead lanes read row 0)
+                            else if (left) v[q] = hit[q] ? sw[from_probe ? row0 + prow[q] : int64_t(by_pos ? bpos[q] : brow[q])] : nw;
+                            else v[q] = live[q] ? sw[row0 + prow[q]] : 0ull;
+                        }
 #pragma unroll
-                        for (int q = 0; q < 4; ++q)
-                            if (live[q]) __builtin_nontemporal_store(v[q], &dw[out_base + uint64_t(int64_t(j0) + q * JT_BLOCK + int64_t(threadIdx.x))]);
+                        for (int q = 0; q < 4; ++q) {
+                            if (!live[q]) continue;
+                            const uint64_t pos = out_base + uint64_t(j0 + q * JT_BLOCK + int64_t(threadIdx.x));
+                            __builtin_nontemporal_store(v[q], &dw[pos]);
+                            if (NULL_EXTEND && vb) vb[pos] = hit[q] ? 1 : 0;
+                        }
                         continue;
                     }
-                    const uint8_t *sv = jc.src_valid[c];
-                    const int dt = jc.dtype[c];
+                    const uint8_t *sv = ec.src_valid[c];
+                    const int dt = ec.dtype[c];
+                    uint8_t *__restrict__ vb = ec.dst_valid_bytes[c];
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         if (!live[q]) continue;
-                        int64_t srow = left ? int64_t(jc.by_pos[c] ? bpos[q] : brow[q]) : row0 + prow[q];
-                        bool ok = sv ? get_bit(sv, srow) : true;
-                        uint64_t v = load_word(src, dt, srow);
-                        uint64_t pos = out_base + uint64_t(int64_t(j0) + q * JT_BLOCK + int64_t(threadIdx.x));
-                        if (jc.dst_words[c]) jc.dst_words[c][pos] = ok ? v : 0;
-                        if (jc.dst_bool_bytes[c]) jc.dst_bool_bytes[c][pos] = (ok && v) ? 1 : 0;
-                        if (jc.dst_valid_bytes[c]) jc.dst_valid_bytes[c][pos] = ok ? 1 : 0;
+                        const uint64_t pos = out_base + uint64_t(j0 + q * JT_BLOCK + int64_t(threadIdx.x));
+                        bool ok = false;
+                        uint64_t v = NULL_EXTEND ? ec.null_word[c] : 0ull;
+                        if (!left || hit[q]) {
+                            const int64_t srow = left && !from_probe ? int64_t(by_pos ? bpos[q] : brow[q]) : row0 + prow[q];
+                            ok = sv ? get_bit(sv, srow) : true;
+                            v = load_word(src, dt, srow); // (the word under a NULL is read and dropped: no branch around the load)
+                            v = ok ? v : 0ull;
+                        }
+                        if (ec.dst_words[c]) ec.dst_words[c][pos] = v;
+                        if (ec.dst_bool_bytes[c]) ec.dst_bool_bytes[c][pos] = (ok && v) ? 1 : 0;
+                        if (vb) vb[pos] = ok ? 1 : 0;
                     }
                 }
             }
@@ -565,6 +626,12 @@ __global__ void __launch_bounds__(JT_BLOCK) probe_write_kernel(const uint64_t *p
             __syncthreads();
         }
     }
+}
+// (8 waves per SIMD, as before the positions became 64-bit: the general instance would otherwise take two scalar registers too many)
+template <bool PLAIN>
+__global__ void __launch_bounds__(JT_BLOCK) __attribute__((amdgpu_waves_per_eu(8))) probe_write_kernel(const uint64_t *pmeta, int64_t n, const uint64_t *tile_offsets,
+                                                               const uint32_t *perm, int direct, ExpandCols ec) {
+    expand_write<PLAIN, false>(pmeta, n, tile_offsets, perm, direct, ec);
 }
 
 } // namespace

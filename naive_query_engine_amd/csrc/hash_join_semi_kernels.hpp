@@ -1,7 +1,7 @@
 // hash_join_semi_kernels.hpp — the device side of the semi and anti hash joins (quirk Q22; included once, by hash_join.hip, after
 // hash_join_outer_kernels.hpp): a probe whose output per row is ONE BIT — the KEEP mask of the compaction kernels — and the pass over
 // the build rows that the marks have (SEMI) or have not (ANTI) seen match.  No per-row word is written anywhere: no build row, no
-// (start, count); the inner and outer kernels are not touched.
+// (start, count).
 #pragma once
 #include "hash_join_outer_kernels.hpp"
 
@@ -28,7 +28,7 @@ struct SemiValid {
 // ANTI:  keeps the rows WITHOUT a partner.  The inversion is part of the lane's own predicate, under row < n: the bits of the rows past
 //        the end stay 0 (a ballot inverted afterwards would set them, and the compaction would emit rows that do not exist).
 // NULLS: a row with a NULL at any key position matches nothing — its hit is cleared before the polarity applies and before any mark.
-// MARKS: a hit sets bit `start` of `marks` exactly as outer_count_kernel does (a plain read first, then atomicOr); needs the start,
+// MARKS: a hit sets bit `start` of `marks` exactly as the count pass (expand_count) does (a plain read first, then atomicOr); needs the start,
 //        so it always goes through lookup_meta.
 // KEEP:  off for the mark-only pass: no keep word, no count.
 template <int FORM, bool ANTI, bool NULLS, bool MARKS, bool KEEP>
@@ -277,8 +277,10 @@ __global__ void __launch_bounds__(256) semi_keep_coop_kernel(const uint64_t *rke
     }
 }
 
-// the build rows whose bit is set (SEMI) or not (ANTI), as a KEEP mask: unmatched_build_kernel's walk with a polarity.  direct tables
-// test bit r; duplicate-key tables look the row's own key up (bkeys) and test bit `start`, the bit every row of that key shares.
+// the build rows whose bit is set (SEMI) or not (ANTI), as the KEEP mask of the compaction kernels (wave per 4096-row tile); <true> is
+// also the outer join's pass over the build rows that no probe batch matched (label join_outer_unmatched).  direct tables test bit r;
+// duplicate-key tables look the row's own key up (bkeys: the build key column — for Utf8 keys re-encoded through the table's
+// dictionary) and test bit `start`, the bit every row of that key shares.
 template <bool ANTI>
 __global__ void __launch_bounds__(256) marked_build_kernel(const uint64_t *bkeys, int64_t n, int64_t ntiles, Lookup L, const uint32_t *marks, uint64_t *keep,
                                                            uint32_t *tile_counts) {

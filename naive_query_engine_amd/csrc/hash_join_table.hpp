@@ -86,14 +86,21 @@ struct FusedCols {
     uint64_t base[MAX_JOIN_COLS];
     int32_t bits[MAX_JOIN_COLS]; // kind 4: bits per entry
 };
-struct JoinCols {
+// the columns of the expand-and-write pass (expand_write: probe_write_kernel / outer_write_kernel), filled from
+// hash_join_expand_plan.hpp's list.  from_probe and null_word are the outer entry's: the inner instances never read them.
+struct ExpandCols {
     int32_t n;
     int32_t n_left;
-    int32_t need_perm;               // some left column is addressed by build row (else: all by position in the sorted row list)
-    int32_t by_pos[MAX_JOIN_COLS];   // left column k: src is the `perm`-ordered copy, addressed by start + match number
+    int32_t need_perm; // some left column is addressed by build row (else: all by position in the sorted row list)
+    int32_t pad;
+    int32_t by_pos[MAX_JOIN_COLS]; // left column k: src is the `perm`-ordered copy, addressed by start + match number
+    // left column k is the build key, taken from the PROBE key column at the probe row (the key of a match is bit-identical on both
+    // sides: a coalesced read instead of a random gather); a NULL-extended row still gets null_word and validity 0
+    int32_t from_probe[MAX_JOIN_COLS];
+    int32_t dtype[MAX_JOIN_COLS];
     const void *src[MAX_JOIN_COLS];
     const uint8_t *src_valid[MAX_JOIN_COLS];
-    int32_t dtype[MAX_JOIN_COLS];
+    uint64_t null_word[MAX_JOIN_COLS]; // the word a NULL-extended row holds (0; -1 for a row-number column that feeds take_utf8)
     uint64_t *dst_words[MAX_JOIN_COLS];
     uint8_t *dst_bool_bytes[MAX_JOIN_COLS];
     uint8_t *dst_valid_bytes[MAX_JOIN_COLS];

@@ -383,6 +383,121 @@ def test_a_probe_tile_beyond_2p32_output_rows_is_out_of_memory(ctx, keep_probe):
     assert ctx.hash_join_probe_outer(jt, miss, 0, keep_probe=keep_probe, marks=marks).num_rows == (4096 if keep_probe else 0)
 
 
+def _free_device_bytes():
+    """hipMemGetInfo of the HIP runtime the library has loaded into this process (a second runtime — torch's — finds no device once
+    the first one holds it); 0 when it cannot be asked"""
+    try:
+        with open("/proc/self/maps") as f:
+            path = next(line.split()[-1] for line in f if "libamdhip64" in line)
+        free, total = C.c_size_t(), C.c_size_t()
+        return int(free.value) if C.CDLL(path).hipMemGetInfo(C.byref(free), C.byref(total)) == 0 else 0
+    except Exception:
+        return 0
+
+
+@pytest.mark.timeout(900)
+@pytest.mark.parametrize("entry", ["inner", "outer", "outer_keep_probe"])
+def test_a_sub_tile_of_exactly_2p31_output_rows(ctx, entry):
+    """2^21 build rows of one key (payload = the row number) probed by 1024 rows of that key: ONE 1024-row sub-tile of the write pass
+    expands to exactly 2^31 output rows, the smallest shape at which a signed 32-bit position inside a sub-tile goes negative (the whole
+    4096-row tile is what is bounded, at 2^32).  The output — one key buffer both key columns share and the payload column, 32 GB — is
+    checked on the device: count, min and max of every column, the exact payload sum, and ten rows at three offsets.
+    Observed on the commit before the inner entry's positions became 64-bit: the inner case failed at the first value check (minimum
+    of the key column 0 instead of 42: 2^31 rows were returned and none had been written — the loop `j0 < int32_t(total)` never ran,
+    no error was raised), the two outer cases passed."""
+    from naive_query_engine_amd import AggregateFunc as A
+
+    if _free_device_bytes() < 48 * 2**30:
+        pytest.skip("needs 48 GB of free device memory")
+    nb, m, key = 1 << 21, 1024, 42
+    lt = ctx.table_from_host([i64(np.full(nb, key)), i64(np.arange(nb))])
+    rt = ctx.table_from_host([i64(np.full(m, key))])
+    jt = ctx.hash_join_build(lt, 0)
+    if entry == "inner":
+        out = ctx.hash_join_probe(jt, rt, 0)
+    else:
+        out = ctx.hash_join_probe_outer(jt, rt, 0, keep_probe=entry == "outer_keep_probe", marks=None)
+    assert out.num_rows == 2**31 and out.num_columns == 3
+    cnt, kmin, kmax, pmin, pmax, psum, rmin, rmax = [float(c.to_numpy()[0]) for c in
+                                                    ctx.aggregate(out, [(A.Count, 0), (A.Min, 0), (A.Max, 0), (A.Min, 1), (A.Max, 1), (A.Sum, 1), (A.Min, 2), (A.Max, 2)]).to_host()]
+    assert cnt == 2.0**31
+    assert kmin == kmax == rmin == rmax == float(key)
+    assert pmin == 0.0 and pmax == float(nb - 1)
+    assert m * nb * (nb - 1) // 2 < 2**53 and psum == float(m * nb * (nb - 1) // 2)  # every partial sum is an integer below 2^53: exact
+    for off in (0, nb - 5, 2**31 - 10):  # probe-row-major, ascending build row inside a probe row
+        k, p, r = [c.to_numpy() for c in ctx.slice(out, off, 10).to_host()]
+        assert (p == (off + np.arange(10)) % nb).all() and (k == key).all() and (r == key).all(), f"{entry}: rows at {off}: {p}"
+    del out
+    gc.collect()
+
+
+# ----------------------------------------------------------------------------- one expand path, two entries
+AGREE_ROWS = [0, 1, 1023, 1024, 1025, 4096, 4097]  # probe rows: the sub-tile (1024) and tile (4096) edges of the two passes
+
+
+def check_entries_agree(ctx, jt, right, rkey, what, duplicates):
+    """hash_join_probe and hash_join_probe_outer(keep_probe=False, marks=None) over one table: dtypes, values, validity bits (and
+    whether a bitmap is there) and null counts.  The outer entry reports the exact null count of every column; the inner entry reports
+    it or -1 (not counted), as it always has — what is compared is the number of NULLs under both outputs."""
+    rt = ctx.table_from_host(right)
+    labels = ("join_probe_count", "join_probe_write", "join_outer_count", "join_outer_write")
+    ctx.timing_enable(True)
+    ctx.timing_reset()
+    try:
+        a = ctx.hash_join_probe(jt, rt, rkey)
+        b = ctx.hash_join_probe_outer(jt, rt, rkey, keep_probe=False, marks=None)
+        launches = [ctx.timing_query(name)[1] for name in labels]
+    finally:
+        ctx.timing_enable(False)
+        ctx.timing_reset()
+    assert a.dtypes() == b.dtypes(), what
+    ga, gb = a.to_host(), b.to_host()
+    oju.assert_same_columns(ga, gb, what)
+    for i, (x, y) in enumerate(zip(ga, gb)):
+        nulls = int(y.length - y.valid_mask().sum())
+        assert int(x.length - x.valid_mask().sum()) == nulls
+        assert int(b.column_info(i).null_count) == nulls and int(a.column_info(i).null_count) in (nulls, -1), f"{what} column {i}"
+    if duplicates:  # one count pass per entry, and one write pass where there is anything to write
+        m, rows = right[rkey].length, a.num_rows
+        assert launches == [int(m > 0), int(rows > 0), int(m > 0), int(rows > 0)], f"{what}: {dict(zip(labels, launches))}"
+    return a.num_rows
+
+
+@pytest.mark.parametrize("form", list(FORMS))
+def test_inner_and_outer_entries_agree_on_every_build_form(ctx, form):
+    make, lkey = FORMS[form]
+    rng = np.random.default_rng(300 + sorted(FORMS).index(form))
+    left = make(rng, 301)
+    lt = ctx.table_from_host(left)
+    jt = ctx.hash_join_build(lt, lkey)
+    for m in AGREE_ROWS:
+        check_entries_agree(ctx, jt, probe_side(rng, left[lkey], m), 1, f"{form} m={m}", form in ("dup_dense", "dup_sparse", "utf8"))
+
+
+def _payload(kind, rng, n):
+    if kind == "plain":
+        return Column.from_numpy(rng.integers(I64.min, I64.max, n, dtype=np.int64))
+    return payload_columns(rng, n)[{"nullable": 0, "boolean": 2, "utf8": 3}[kind]]
+
+
+@pytest.mark.parametrize("m", AGREE_ROWS)
+@pytest.mark.parametrize("kind", ["plain", "nullable", "boolean", "utf8"])
+def test_inner_and_outer_entries_agree_on_duplicate_keys(ctx, kind, m):
+    """key k occurs k % 5 + 1 times on the build side: a 1024-row sub-tile expands to about 3000 rows — several steps of the write
+    loop (1024 output rows each) — and the output base of every later sub-tile sits anywhere inside its 128-byte line (base & 15)"""
+    rng = np.random.default_rng(900 + m)
+    keys = np.repeat(np.arange(200), np.arange(200) % 5 + 1)
+    keys = keys[rng.permutation(keys.size)]
+    left = [i64(keys), _payload(kind, rng, keys.size)]
+    right = [_payload(kind, rng, m), i64(rng.integers(0, 250, m))]  # a fifth of the probe keys match nothing
+    lt = ctx.table_from_host(left)
+    jt = ctx.hash_join_build(lt, 0)
+    rows = check_entries_agree(ctx, jt, right, 1, f"{kind} m={m}", True)
+    assert rows == int(np.bincount(keys, minlength=250)[right[1].to_numpy()].sum())
+    if m >= 1023:
+        assert rows > 2 * 1024
+
+
 # ----------------------------------------------------------------------------- a seeded sweep
 def _random_case(seed):
     rng = np.random.default_rng(5000 + seed)

@@ -38,7 +38,7 @@ def kernels(path):
     dem = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True, check=True).stdout.split("\n")
     res = {}
     for n, d in zip(names, dem):
-        d = d.replace("nqe::agg::(anonymous namespace)::", "").replace("nqe::agg::", "").replace("nqe::", "")
+        d = d.replace("nqe::agg::(anonymous namespace)::", "").replace("nqe::agg::", "").replace("nqe::", "").replace("(anonymous namespace)::", "")
         res[re.sub(r"^void |\(.*$", "", d)] = out[n]
     return res
 
