@@ -122,8 +122,13 @@ typedef struct nqe_column {
  * (expression/unary.rs:46-78; `name` and `return_type` are ignored by evaluate and have no
  * place in the encoding). A BINARY node pops two operands (right on top), a UNARY node pops
  * one; each pushes its result. A tree is valid when evaluating the nodes left-to-right on a
- * stack leaves exactly one value. */
-typedef enum nqe_expr_kind { NQE_EXPR_COLUMN = 0, NQE_EXPR_LITERAL = 1, NQE_EXPR_BINARY = 2, NQE_EXPR_UNARY = 3 } nqe_expr_kind;
+ * stack leaves exactly one value.
+ * A STRING node (quirk Q25: "the string functions, given a body") is this library's own beside
+ * the reference's: it pops one Utf8 operand like a UNARY node, its `op` is a nqe_unary_operator
+ * naming one of TRIM, LTRIM, RTRIM, CHARACTER_LENGTH, LOWER, UPPER and REVERSE, and it pushes a
+ * Utf8 value (Int64 for CHARACTER_LENGTH). A UNARY node over the same functions stays what the
+ * reference's todo!() is: NQE_ERR_NOT_SUPPORTED. */
+typedef enum nqe_expr_kind { NQE_EXPR_COLUMN = 0, NQE_EXPR_LITERAL = 1, NQE_EXPR_BINARY = 2, NQE_EXPR_UNARY = 3, NQE_EXPR_STRING = 4 } nqe_expr_kind;
 
 /* same order as `enum Operator` (logical_plan/expression.rs:335-362) */
 typedef enum nqe_operator {
@@ -145,7 +150,8 @@ typedef enum nqe_operator {
 /* same order as `enum UnaryOperator` (logical_plan/expression.rs:392-422). Only the four math
  * functions have a body in the reference (unary.rs:92-107), and only over Float64; quirk Q16:
  * TAN evaluates the COSINE (unary.rs:96). The string functions are todo!() there and
- * NQE_ERR_NOT_SUPPORTED here. */
+ * NQE_ERR_NOT_SUPPORTED here under a UNARY node; seven of them have a body under a STRING node
+ * (see nqe_expr_evaluate). */
 typedef enum nqe_unary_operator {
     NQE_UNARY_ABS = 0,
     NQE_UNARY_SIN = 1,
@@ -165,7 +171,7 @@ typedef enum nqe_unary_operator {
 
 typedef struct nqe_expr_node {
     int32_t kind;    /* nqe_expr_kind */
-    int32_t op;      /* BINARY: nqe_operator; UNARY: nqe_unary_operator */
+    int32_t op;      /* BINARY: nqe_operator; UNARY and STRING: nqe_unary_operator */
     int32_t column;  /* COLUMN: index into the input batch */
     int32_t dtype;   /* LITERAL: nqe_dtype of the ScalarValue */
     int32_t is_null; /* LITERAL: 1 = ScalarValue::X(None) */
@@ -456,7 +462,26 @@ nqe_status nqe_sharded_selection_projection_execute(nqe_comm *comm, const nqe_ta
  * divisor → NQE_ERR_ARROW; arithmetic on Boolean/Utf8 → NQE_ERR_NOT_SUPPORTED; a unary node
  * over anything but Float64 or any of the string functions → NQE_ERR_NOT_SUPPORTED; a unary
  * node without an operand or with an `op` outside nqe_unary_operator →
- * NQE_ERR_INVALID_ARGUMENT. All of these are decided before anything is allocated or launched. */
+ * NQE_ERR_INVALID_ARGUMENT. All of these are decided before anything is allocated or launched.
+ * String nodes (NQE_EXPR_STRING, quirk Q25) are defined on the BYTES between a slot's two
+ * offsets; validity is never read, so the bytes under a NULL are transformed like any other and
+ * the result is total and deterministic. TRIM / LTRIM / RTRIM strip bytes 0x20 (and nothing
+ * else: tab, newline, U+00A0 and U+3000 stay) from both ends, the front or the back. LOWER /
+ * UPPER map the bytes A-Z / a-z and leave every other byte, every byte of a multi-byte sequence
+ * included, as it is: ASCII only, the length never changes (Rust's to_lowercase would change
+ * it). CHARACTER_LENGTH is Int64: the number of bytes b with (b & 0xC0) != 0x80, the number of
+ * code points of valid UTF-8. REVERSE reverses the order of units and keeps the bytes inside a
+ * unit in order; byte i starts a unit when i == 0, or it is no continuation byte, or bytes i-1,
+ * i-2 and i-3 all exist and are continuation bytes (units are 1-4 bytes: the code points of
+ * valid UTF-8, and a fixed permutation of the string's own bytes otherwise). The result has the
+ * operand's validity (shared when it may be, else copied) and null_count; a literal operand is
+ * expanded to `in.num_rows` rows, a NULL Utf8 literal to an all-NULL column. The operand may be
+ * a STRING node; a Utf8 result may feed a Utf8 compare, CHARACTER_LENGTH Int64 arithmetic and
+ * compares. A tree that holds a STRING node is evaluated node at a time. Errors, in this order,
+ * before anything is allocated or launched: no operand → NQE_ERR_INVALID_ARGUMENT; `op` outside
+ * nqe_unary_operator → NQE_ERR_INVALID_ARGUMENT; `op` one of ABS..TAN →
+ * NQE_ERR_INVALID_ARGUMENT; REPEAT, REPLACE or SUBSTR (they need arguments a one-operand node
+ * cannot carry) → NQE_ERR_NOT_SUPPORTED; an operand that is not Utf8 → NQE_ERR_NOT_SUPPORTED. */
 nqe_status nqe_expr_evaluate(nqe_ctx *ctx, const nqe_table *in, const nqe_expr_node *nodes,
                              int32_t num_nodes, nqe_table **out);
 

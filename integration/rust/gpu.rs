@@ -49,11 +49,12 @@ use arrow::record_batch::RecordBatch;
 use crate::catalog::Catalog;
 use crate::datasource::{TableRef, TableSource};
 use crate::error::{ErrorCode, Result};
-use crate::logical_plan::expression::{AggregateFunc, Column, ScalarValue};
+use crate::datatype::ColumnValue;
+use crate::logical_plan::expression::{AggregateFunc, Column, ScalarValue, UnaryOperator};
 use crate::logical_plan::plan::JoinType;
 use crate::logical_plan::schema::{NaiveField, NaiveSchema};
 use crate::physical_plan::{
-    ColumnExpr, CrossJoin, HashJoin, NestedLoopJoin, PhysicalAggregatePlan, PhysicalBinaryExpr, PhysicalExprRef, PhysicalLimitPlan, PhysicalLiteralExpr, PhysicalOffsetPlan,
+    ColumnExpr, CrossJoin, HashJoin, NestedLoopJoin, PhysicalAggregatePlan, PhysicalBinaryExpr, PhysicalExpr, PhysicalExprRef, PhysicalLimitPlan, PhysicalLiteralExpr, PhysicalOffsetPlan,
     PhysicalPlan, PhysicalPlanRef, PhysicalUnaryExpr, ProjectionPlan, ScanPlan, SelectionPlan,
 };
 
@@ -101,6 +102,7 @@ pub enum NqeComm {}
 // nqe_expr_kind; nqe_unary_operator is `enum UnaryOperator` in declaration order (expression.rs:392-422): Abs = 0, Sin = 1, Cos = 2, Tan = 3,
 // Trim = 4, LTrim = 5, RTrim = 6, CharacterLength = 7, Lower = 8, Upper = 9, Repeat = 10, Replace = 11, Reverse = 12, Substr = 13
 const NQE_EXPR_COLUMN: i32 = 0; const NQE_EXPR_LITERAL: i32 = 1; const NQE_EXPR_BINARY: i32 = 2; const NQE_EXPR_UNARY: i32 = 3;
+const NQE_EXPR_STRING: i32 = 4; // quirk Q25: the shim's own PhysicalStringExpr below
 const NQE_BOOLEAN: i32 = 1; const NQE_INT64: i32 = 2; const NQE_UINT64: i32 = 3; const NQE_FLOAT64: i32 = 4; const NQE_UTF8: i32 = 5;
 
 extern "C" {
@@ -357,6 +359,21 @@ impl PhysicalPlan for GpuScanPlan {
 }
 
 // ------------------------------------------------------------------ expressions → flat post-order nodes
+/// The shim's own expression beside the reference's (quirk Q25): Trim, LTrim, RTrim, CharacterLength, Lower, Upper or Reverse of
+/// `enum UnaryOperator` with a body, over a Utf8 operand — Utf8, or Int64 for CharacterLength.  It exists on the device only: a plan
+/// that holds one is executed through the Gpu* operators, which flatten it; PhysicalUnaryExpr over the same functions stays todo!().
+#[derive(Debug)]
+pub struct PhysicalStringExpr { pub expr: PhysicalExprRef, pub func: UnaryOperator }
+impl PhysicalStringExpr {
+    pub fn create(expr: PhysicalExprRef, func: UnaryOperator) -> PhysicalExprRef { Arc::new(Self { expr, func }) }
+}
+impl PhysicalExpr for PhysicalStringExpr {
+    fn as_any(&self) -> &dyn Any { self }
+    fn evaluate(&self, _input: &RecordBatch) -> Result<ColumnValue> {
+        Err(ErrorCode::NotSupported(format!("{:?} as a string function is evaluated on the device only (nqe_expr_evaluate)", self.func)))
+    }
+}
+
 fn zero_node() -> NqeExprNode { NqeExprNode { kind: 0, op: 0, column: 0, dtype: 0, is_null: 0, utf8_length: 0, value: NqeValue { i64_: 0 } } }
 
 /// ColumnExpr → column index: prefer idx, else the FIRST field with that name (column.rs:39-57, quirk Q12)
@@ -400,6 +417,9 @@ fn flatten(e: &PhysicalExprRef, schema: &NaiveSchema, out: &mut Vec<NqeExprNode>
         // cosine on the device as it is there (quirk Q16); the string functions come back as NotSupported from the library
         flatten(&u.expr, schema, out, keep)?;
         out.push(NqeExprNode { kind: NQE_EXPR_UNARY, op: u.func.clone() as i32, ..zero_node() }); // UnaryOperator is declared in nqe_unary_operator's order
+    } else if let Some(s) = e.as_any().downcast_ref::<PhysicalStringExpr>() {
+        flatten(&s.expr, schema, out, keep)?;
+        out.push(NqeExprNode { kind: NQE_EXPR_STRING, op: s.func.clone() as i32, ..zero_node() });
     } else {
         return Err(ErrorCode::NotSupported("expression kind has no device implementation (cast)".to_string()));
     }

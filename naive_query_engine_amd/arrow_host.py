@@ -207,6 +207,7 @@ class NqeCsvOptions(C.Structure):
 
 
 EXPR_COLUMN, EXPR_LITERAL, EXPR_BINARY, EXPR_UNARY = 0, 1, 2, 3
+EXPR_STRING = 4  # quirk Q25: a string function with a body (NQE_EXPR_STRING); `op` is a UnaryOperator
 HOST, DEVICE = 0, 1
 
 _WORD_NP = {DType.INT64: np.int64, DType.UINT64: np.uint64, DType.FLOAT64: np.float64}
@@ -541,6 +542,13 @@ def node_binary(op: Operator) -> NqeExprNode:
 def node_unary(func: "UnaryOperator") -> NqeExprNode:
     n = NqeExprNode()
     n.kind = EXPR_UNARY
+    n.op = int(func)
+    return n
+
+
+def node_string(func: "UnaryOperator") -> NqeExprNode:
+    n = NqeExprNode()
+    n.kind = EXPR_STRING
     n.op = int(func)
     return n
 

@@ -529,6 +529,7 @@ bool AggRun::prepare() {
         if (kinfo.out_dtype == NQE_UTF8) {
             // group by a String column (aggregate/mod.rs:170-216): encode strings to representative-row codes,
             // then the Int64 path; keys_out returns the strings of the representatives
+            if (!kinfo.simple || kinfo.s.nops) fail(NQE_ERR_NOT_SUPPORTED, "group by: a Utf8 key must be a bare column"); // (`trim(s)`, a Utf8 literal)
             utf8_key = true;
             Utf8Dict dict;
             utf8_src = in->cols[size_t(kinfo.s.col)];

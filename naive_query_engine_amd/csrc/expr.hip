@@ -116,6 +116,12 @@ Value eval_node(nqe_ctx *ctx, const nqe_table *in, const std::vector<Node> &t, i
         }
         return v;
     }
+    if (x.kind == NQE_EXPR_STRING) { // quirk Q25 (string_fn.hip): Utf8, or Int64 for CHARACTER_LENGTH, with the operand's validity
+        Value c = eval_node(ctx, in, t, x.left);
+        if (c.is_lit) c.col = utf8_literal_column(ctx, c.lit_str, c.lit_null, in->rows);
+        v.col = string_fn(ctx, x.op, c.col);
+        return v;
+    }
     Value l = eval_node(ctx, in, t, x.left);
     Value r = eval_node(ctx, in, t, x.right);
     const int64_t n = in->rows;

@@ -44,7 +44,7 @@ struct Node {
 bool is_compare(int op) { return op >= NQE_OP_EQ && op <= NQE_OP_GT_EQ; }
 bool is_logic(int op) { return op == NQE_OP_AND || op == NQE_OP_OR; }
 bool is_arith(int op) { return op >= NQE_OP_PLUS && op <= NQE_OP_MODULOS; }
-bool is_op_node(int kind) { return kind == NQE_EXPR_BINARY || kind == NQE_EXPR_UNARY; } // a node with operands: a step of a program
+bool is_op_node(int kind) { return kind == NQE_EXPR_BINARY || kind == NQE_EXPR_UNARY || kind == NQE_EXPR_STRING; } // a node with operands: a step of a program
 
 // ------------------------------------------------------------------ fused whole-tree evaluation: the stack machine's program
 // One instruction per BINARY or UNARY node (post-order), whose operands are a literal, a column word (slot k of the program's distinct
@@ -169,6 +169,16 @@ std::vector<Node> parse(const ExprView &in, const nqe_expr_node *nodes, int n, i
             if (t[size_t(x.left)].out_dtype != NQE_FLOAT64) // unary_arith_op! `_ => unimplemented!()` (unary.rs:41)
                 fail(NQE_ERR_NOT_SUPPORTED, "unary math functions on this type are unimplemented!() (unary.rs:41)");
             x.out_dtype = NQE_FLOAT64;
+        } else if (nd.kind == NQE_EXPR_STRING) { // quirk Q25: the string functions, given a body (string_fn.hip)
+            if (st.empty()) fail(NQE_ERR_INVALID_ARGUMENT, "malformed expression");
+            x.left = st.back(); st.pop_back();
+            x.op = nd.op;
+            if (x.op < NQE_UNARY_ABS || x.op > NQE_UNARY_SUBSTR) fail(NQE_ERR_INVALID_ARGUMENT, "unknown string function");
+            if (x.op <= NQE_UNARY_TAN) fail(NQE_ERR_INVALID_ARGUMENT, "a math function under a string node (it belongs under NQE_EXPR_UNARY)");
+            if (x.op == NQE_UNARY_REPEAT || x.op == NQE_UNARY_REPLACE || x.op == NQE_UNARY_SUBSTR)
+                fail(NQE_ERR_NOT_SUPPORTED, "repeat / replace / substr need arguments a one-operand node cannot carry");
+            if (t[size_t(x.left)].out_dtype != NQE_UTF8) fail(NQE_ERR_NOT_SUPPORTED, "a string function over an operand that is not Utf8");
+            x.out_dtype = x.op == NQE_UNARY_CHARACTER_LENGTH ? NQE_INT64 : NQE_UTF8;
         } else {
             fail(NQE_ERR_INVALID_ARGUMENT, "unknown expression node kind");
         }
@@ -233,7 +243,7 @@ bool match_simple(const std::vector<Node> &t, int i, SimpleExpr *s) {
         for (int k = 0; k < SIMPLE_MAX_OPS; ++k) s->aux[k].pow2_shift = s->aux[k].more = -1;
         return true; // a bare column of any type (Utf8 included) passes through
     }
-    if (x.kind != NQE_EXPR_BINARY || is_logic(x.op)) return false;
+    if (x.kind != NQE_EXPR_BINARY || is_logic(x.op)) return false; // (a UNARY or STRING step anywhere below ends the chain here too)
     const Node &l = t[size_t(x.left)], &r = t[size_t(x.right)];
     bool lit_left;
     int sub;
@@ -268,6 +278,7 @@ bool build_program(const ExprView &in, const std::vector<Node> &t, int root, ExP
         st.pop_back();
         const Node &x = t[size_t(i)];
         if (!is_op_node(x.kind)) continue;
+        if (x.kind == NQE_EXPR_STRING) return false; // the machine works on 8-byte words: a tree with a string step anywhere goes node at a time
         if (done) { order.push_back(i); continue; }
         st.push_back({i, true});
         if (x.kind == NQE_EXPR_BINARY) st.push_back({x.right, false});
@@ -446,7 +457,7 @@ bool match_conj(const ExprView &in, const nqe_expr_node *nodes, int n, ConjPred 
     // first node of the subtree that ends at node i
     int start[MAXN], stack[MAXN], sp = 0;
     for (int i = 0; i < n; ++i) {
-        if (nodes[i].kind == NQE_EXPR_UNARY) return false; // (a test is `col [arith lit] cmp lit`: no one-operand step; such trees go through expr_tree_kernel)
+        if (nodes[i].kind == NQE_EXPR_UNARY || nodes[i].kind == NQE_EXPR_STRING) return false; // (a test is `col [arith lit] cmp lit`: no one-operand step; such trees go through expr_tree_kernel, or node at a time)
         if (nodes[i].kind == NQE_EXPR_BINARY) {
             if (sp < 2) return false;
             sp -= 2;

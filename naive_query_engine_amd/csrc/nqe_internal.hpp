@@ -328,6 +328,9 @@ KeepMask finish_mask(nqe_ctx *ctx, KeepMask km, BufRef tile_counts);
 DevColumn utf8_compare(nqe_ctx *ctx, int op, const DevColumn *lcol, const std::string &llit, bool llit_null, const DevColumn *rcol,
                        const std::string &rlit, bool rlit_null, int64_t n);
 DevColumn utf8_literal_column(nqe_ctx *ctx, const std::string &lit, bool lit_null, int64_t n);
+// string_fn.hip: one string function of an NQE_EXPR_STRING node (`op`: TRIM, LTRIM, RTRIM, CHARACTER_LENGTH, LOWER, UPPER or REVERSE of
+// nqe_unary_operator, checked by the parser) over the Utf8 column `src`; Utf8, or Int64 for CHARACTER_LENGTH, with src's validity
+DevColumn string_fn(nqe_ctx *ctx, int op, const DevColumn &src);
 // general tree `nodes` over the rows of `km`, compacted in the same pass; false = does not fit the stack machine
 bool evaluate_expr_compacted(nqe_ctx *ctx, const nqe_table *in, const nqe_expr_node *nodes, int n, const KeepMask &km, DevColumn *result);
 // the whole projection list behind a selection in ONE run-time specialised kernel (expr_jit.hpp); false when the list does not fit it

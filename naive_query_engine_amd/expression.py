@@ -15,7 +15,7 @@ from __future__ import annotations
 from typing import List, Optional, Sequence
 
 from .arrow_host import (ErrorCode, Field, NqeExprNode, Operator, ScalarValue, Status, UnaryOperator, node_binary, node_column,
-                         node_literal, node_unary)
+                         node_literal, node_string, node_unary)
 
 
 class PhysicalExpr:
@@ -112,6 +112,30 @@ class PhysicalUnaryExpr(PhysicalExpr):
         return f"{self.func.name}({self.expr!r})"
 
 
+STRING_FUNCTIONS = (UnaryOperator.Trim, UnaryOperator.LTrim, UnaryOperator.RTrim, UnaryOperator.CharacterLength, UnaryOperator.Lower,
+                    UnaryOperator.Upper, UnaryOperator.Reverse)
+
+
+class PhysicalStringExpr(PhysicalExpr):
+    """This package's own node beside the reference's (quirk Q25): one of the string functions of `enum UnaryOperator` that really
+    are unary — Trim, LTrim, RTrim, CharacterLength, Lower, Upper, Reverse — with a body, over a Utf8 operand.  PhysicalUnaryExpr over
+    the same functions stays what the reference's todo!() is (NotSupported).  Any UnaryOperator is taken here and encoded as it is:
+    the library refuses the others, as it refuses everything else about an expression."""
+
+    def __init__(self, expr: PhysicalExpr, func: UnaryOperator):
+        self.expr, self.func = expr, UnaryOperator(func)
+
+    @staticmethod
+    def create(expr: PhysicalExpr, func: UnaryOperator) -> "PhysicalStringExpr":
+        return PhysicalStringExpr(expr, func)
+
+    def flatten(self, fields):
+        return self.expr.flatten(fields) + [node_string(self.func)]
+
+    def __repr__(self):
+        return f"{self.func.name}({self.expr!r})"
+
+
 # small conveniences for tests / bench (not part of the reference surface)
 def col(i_or_name) -> ColumnExpr:
     return ColumnExpr.try_create(None, i_or_name) if isinstance(i_or_name, int) else ColumnExpr.try_create(i_or_name, None)
@@ -143,3 +167,7 @@ def binop(l, op, r) -> PhysicalBinaryExpr:
 
 def unop(func, e) -> PhysicalUnaryExpr:
     return PhysicalUnaryExpr.create(e, func, UnaryOperator(func).name.lower(), None)
+
+
+def strop(func, e) -> PhysicalStringExpr:
+    return PhysicalStringExpr.create(e, func)

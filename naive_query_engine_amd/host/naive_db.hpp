@@ -305,6 +305,25 @@ struct PhysicalUnaryExpr : PhysicalExpr { // unary.rs:46-109
     }
 };
 
+// This mirror's own node beside the reference's (quirk Q25): Trim, LTrim, RTrim, CharacterLength, Lower, Upper or Reverse with a body, over
+// a Utf8 operand (Int64 for CharacterLength, else Utf8).  PhysicalUnaryExpr over the same functions stays NotSupported, as unary.rs:97-106.
+struct PhysicalStringExpr : PhysicalExpr {
+    PhysicalExprRef expr;
+    UnaryOperator func;
+    static PhysicalExprRef create(PhysicalExprRef e, UnaryOperator func) {
+        auto s = std::make_shared<PhysicalStringExpr>();
+        s->expr = std::move(e); s->func = func;
+        return s;
+    }
+    void flatten(const NaiveSchema &schema, std::vector<nqe_expr_node> &out) const override {
+        expr->flatten(schema, out);
+        nqe_expr_node n{};
+        n.kind = NQE_EXPR_STRING;
+        n.op = int32_t(func);
+        out.push_back(n);
+    }
+};
+
 // ---------------------------------------------------------------- datasource/memory.rs
 struct TableSource {
     virtual ~TableSource() = default;
@@ -1223,12 +1242,19 @@ struct WindowFunctionEx {
     static DataType static_dtype(const PhysicalExprRef &e, const NaiveSchema &schema) {
         if (const ColumnExpr *c = e->as_column()) return schema.field(c->resolve(schema)).data_type;
         std::vector<nqe_expr_node> nodes;
-        e->flatten(schema, nodes); // postfix: the first node is the left-most leaf
-        if (!nodes.empty() && nodes.back().kind == NQE_EXPR_UNARY) return DataType::Float64;
-        if (!nodes.empty() && nodes.back().kind == NQE_EXPR_BINARY && (nodes.back().op <= NQE_OP_GT_EQ || nodes.back().op >= NQE_OP_AND)) return DataType::Boolean;
-        if (!nodes.empty() && nodes[0].kind == NQE_EXPR_LITERAL) return DataType(nodes[0].dtype);
-        if (!nodes.empty() && nodes[0].kind == NQE_EXPR_COLUMN) return schema.field(size_t(nodes[0].column)).data_type;
-        return DataType::Float64;
+        e->flatten(schema, nodes); // postfix: a stack of dtypes — an arithmetic node has its left operand's (Q6: no coercion)
+        std::vector<DataType> st;
+        for (const nqe_expr_node &n : nodes) {
+            if (n.kind == NQE_EXPR_COLUMN) st.push_back(schema.field(size_t(n.column)).data_type);
+            else if (n.kind == NQE_EXPR_LITERAL) st.push_back(DataType(n.dtype));
+            else if (n.kind == NQE_EXPR_UNARY && !st.empty()) st.back() = DataType::Float64;
+            else if (n.kind == NQE_EXPR_STRING && !st.empty()) st.back() = n.op == NQE_UNARY_CHARACTER_LENGTH ? DataType::Int64 : DataType::Utf8; // quirk Q25
+            else if (n.kind == NQE_EXPR_BINARY && st.size() >= 2) {
+                st.pop_back();
+                if (n.op <= NQE_OP_GT_EQ || n.op >= NQE_OP_AND) st.back() = DataType::Boolean;
+            }
+        }
+        return st.empty() ? DataType::Float64 : st.back();
     }
     NaiveField data_field(const NaiveSchema &schema) const {
         if (func == NQE_WINX_NTILE) return NaiveField(std::nullopt, "ntile(" + std::to_string(buckets) + ")", DataType::UInt64, false);

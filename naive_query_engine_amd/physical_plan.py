@@ -21,8 +21,8 @@ from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple
 
 from . import capi
-from .arrow_host import AggregateFunc, Column, DType, ErrorCode, Field, Operator, RecordBatch, ScalarValue, SetOp, Status, WindowFrame, WindowFrameEx, WindowFunc, WindowFuncEx
-from .expression import ColumnExpr, PhysicalBinaryExpr, PhysicalExpr, PhysicalLiteralExpr
+from .arrow_host import AggregateFunc, Column, DType, ErrorCode, Field, Operator, RecordBatch, ScalarValue, SetOp, Status, UnaryOperator, WindowFrame, WindowFrameEx, WindowFunc, WindowFuncEx
+from .expression import ColumnExpr, PhysicalBinaryExpr, PhysicalExpr, PhysicalLiteralExpr, PhysicalStringExpr
 
 NaiveSchema = List[Field]  # src/logical_plan/schema.rs (qualifiers are ignored at physical planning, Q12)
 
@@ -903,7 +903,10 @@ _COMPARISONS = (Operator.Eq, Operator.NotEq, Operator.Lt, Operator.LtEq, Operato
 
 
 def _static_dtype(expr: PhysicalExpr, schema: NaiveSchema) -> DType:
-    """the dtype an expression evaluates to (Q6: no coercion, so an arithmetic node has its left operand's; a unary function Float64)"""
+    """the dtype an expression evaluates to (Q6: no coercion, so an arithmetic node has its left operand's; a unary function Float64; a string
+    function Utf8, CharacterLength Int64)"""
+    if isinstance(expr, PhysicalStringExpr):
+        return DType.INT64 if expr.func == UnaryOperator.CharacterLength else DType.UTF8
     if isinstance(expr, ColumnExpr):
         return schema[expr.resolve(schema)].dtype
     if isinstance(expr, PhysicalLiteralExpr):
