@@ -127,8 +127,12 @@ typedef struct nqe_column {
  * the reference's: it pops one Utf8 operand like a UNARY node, its `op` is a nqe_unary_operator
  * naming one of TRIM, LTRIM, RTRIM, CHARACTER_LENGTH, LOWER, UPPER and REVERSE, and it pushes a
  * Utf8 value (Int64 for CHARACTER_LENGTH). A UNARY node over the same functions stays what the
- * reference's todo!() is: NQE_ERR_NOT_SUPPORTED. */
-typedef enum nqe_expr_kind { NQE_EXPR_COLUMN = 0, NQE_EXPR_LITERAL = 1, NQE_EXPR_BINARY = 2, NQE_EXPR_UNARY = 3, NQE_EXPR_STRING = 4 } nqe_expr_kind;
+ * reference's todo!() is: NQE_ERR_NOT_SUPPORTED.
+ * A STRING_ARGS node (quirk Q26: "the string functions with arguments") carries the last three:
+ * its `op` is NQE_UNARY_SUBSTR, NQE_UNARY_REPLACE (both pop THREE values) or NQE_UNARY_REPEAT
+ * (pops TWO); the string operand is deepest, the last argument on top; it pushes a Utf8 value.
+ * In postfix: `s start len SUBSTR`, `s n REPEAT`, `s from to REPLACE`. */
+typedef enum nqe_expr_kind { NQE_EXPR_COLUMN = 0, NQE_EXPR_LITERAL = 1, NQE_EXPR_BINARY = 2, NQE_EXPR_UNARY = 3, NQE_EXPR_STRING = 4, NQE_EXPR_STRING_ARGS = 5 } nqe_expr_kind;
 
 /* same order as `enum Operator` (logical_plan/expression.rs:335-362) */
 typedef enum nqe_operator {
@@ -151,7 +155,7 @@ typedef enum nqe_operator {
  * functions have a body in the reference (unary.rs:92-107), and only over Float64; quirk Q16:
  * TAN evaluates the COSINE (unary.rs:96). The string functions are todo!() there and
  * NQE_ERR_NOT_SUPPORTED here under a UNARY node; seven of them have a body under a STRING node
- * (see nqe_expr_evaluate). */
+ * and REPEAT, REPLACE and SUBSTR under a STRING_ARGS node (see nqe_expr_evaluate). */
 typedef enum nqe_unary_operator {
     NQE_UNARY_ABS = 0,
     NQE_UNARY_SIN = 1,
@@ -481,7 +485,37 @@ nqe_status nqe_sharded_selection_projection_execute(nqe_comm *comm, const nqe_ta
  * before anything is allocated or launched: no operand → NQE_ERR_INVALID_ARGUMENT; `op` outside
  * nqe_unary_operator → NQE_ERR_INVALID_ARGUMENT; `op` one of ABS..TAN →
  * NQE_ERR_INVALID_ARGUMENT; REPEAT, REPLACE or SUBSTR (they need arguments a one-operand node
- * cannot carry) → NQE_ERR_NOT_SUPPORTED; an operand that is not Utf8 → NQE_ERR_NOT_SUPPORTED. */
+ * cannot carry) → NQE_ERR_NOT_SUPPORTED; an operand that is not Utf8 → NQE_ERR_NOT_SUPPORTED.
+ * String nodes with arguments (NQE_EXPR_STRING_ARGS, quirk Q26): SUBSTR(s, start, len),
+ * REPEAT(s, n), REPLACE(s, from, to). `s` is any Utf8 value (a column, a literal expanded as a
+ * STRING node expands it, a STRING node or another STRING_ARGS node); `start`, `len` and `n` are
+ * Int64 values of any form (a column, a literal, any Int64-valued subtree); `from` and `to` are
+ * Utf8 LITERALS (NULL allowed). Like Q25's functions these are defined on the bytes between a
+ * slot's two offsets and are total and deterministic. Byte j of a string has the character
+ * number c(j) = max(1, number of bytes k <= j with (s[k] & 0xC0) != 0x80): code points for valid
+ * UTF-8, a fixed partition otherwise, continuation bytes at the very front belonging to
+ * character 1. SUBSTR keeps the bytes with max(start, 1) <= c(j) < start + len, the sum
+ * saturating at INT64_MAX ("to the end" is len = INT64_MAX; there is no two-operand form);
+ * len <= 0, a start past the end and start + len <= 1 give the empty string, nothing is an
+ * error, and the result is one contiguous byte range. REPEAT is max(n, 0) copies of the bytes.
+ * REPLACE turns the leftmost non-overlapping occurrences of the bytes of `from`, found left to
+ * right (each search resumes behind the previous match), into the bytes of `to`; matching is by
+ * bytes, and an empty `from` leaves the string as it is. Result row i is NULL iff any operand
+ * is NULL at i (a NULL literal makes the whole column NULL); null_count is exact. Unlike Q25's
+ * kernels these READ validity: a NULL result row is the EMPTY string — except where the result
+ * shares the operand's offsets and so cannot empty a slot (REPLACE with |to| == |from|, whose
+ * bytes under a NULL are transformed like any other, and REPLACE with an empty `from` or a
+ * `from` longer than the operand's data, which returns the operand's own buffers). When only `s`
+ * can be NULL its validity is carried (shared when it may be, else copied). A result of more
+ * than 2^31-1 bytes fails with NQE_ERR_ARROW ("offset overflow"): lengths and their total are
+ * computed in 64 bits, the failure comes before the data buffer is allocated, and the context
+ * stays usable. Zero rows or zero result bytes return a well-formed column. A tree that holds
+ * the node is evaluated node at a time. Errors, in this order, before anything is allocated or
+ * launched: `op` outside nqe_unary_operator → NQE_ERR_INVALID_ARGUMENT; `op` not REPEAT,
+ * REPLACE or SUBSTR → NQE_ERR_INVALID_ARGUMENT; fewer values than the function pops →
+ * NQE_ERR_INVALID_ARGUMENT; `s` not Utf8 → NQE_ERR_NOT_SUPPORTED; a SUBSTR or REPEAT argument
+ * that is not Int64 (UInt64, Float64, Boolean, Utf8, a Null-typed literal) →
+ * NQE_ERR_NOT_SUPPORTED; a REPLACE argument that is not a Utf8 literal → NQE_ERR_NOT_SUPPORTED. */
 nqe_status nqe_expr_evaluate(nqe_ctx *ctx, const nqe_table *in, const nqe_expr_node *nodes,
                              int32_t num_nodes, nqe_table **out);
 

@@ -103,6 +103,7 @@ pub enum NqeComm {}
 // Trim = 4, LTrim = 5, RTrim = 6, CharacterLength = 7, Lower = 8, Upper = 9, Repeat = 10, Replace = 11, Reverse = 12, Substr = 13
 const NQE_EXPR_COLUMN: i32 = 0; const NQE_EXPR_LITERAL: i32 = 1; const NQE_EXPR_BINARY: i32 = 2; const NQE_EXPR_UNARY: i32 = 3;
 const NQE_EXPR_STRING: i32 = 4; // quirk Q25: the shim's own PhysicalStringExpr below
+const NQE_EXPR_STRING_ARGS: i32 = 5; // quirk Q26: the shim's own PhysicalStringArgsExpr below
 const NQE_BOOLEAN: i32 = 1; const NQE_INT64: i32 = 2; const NQE_UINT64: i32 = 3; const NQE_FLOAT64: i32 = 4; const NQE_UTF8: i32 = 5;
 
 extern "C" {
@@ -374,6 +375,21 @@ impl PhysicalExpr for PhysicalStringExpr {
     }
 }
 
+/// The shim's own expression beside the reference's (quirk Q26): Substr(s, start, len), Repeat(s, n) or Replace(s, from, to) of
+/// `enum UnaryOperator` with a body, over a Utf8 operand and its arguments (Int64-valued for Substr and Repeat, Utf8 literals for
+/// Replace) — Utf8.  Like PhysicalStringExpr it exists on the device only.
+#[derive(Debug)]
+pub struct PhysicalStringArgsExpr { pub func: UnaryOperator, pub expr: PhysicalExprRef, pub args: Vec<PhysicalExprRef> }
+impl PhysicalStringArgsExpr {
+    pub fn create(func: UnaryOperator, expr: PhysicalExprRef, args: Vec<PhysicalExprRef>) -> PhysicalExprRef { Arc::new(Self { func, expr, args }) }
+}
+impl PhysicalExpr for PhysicalStringArgsExpr {
+    fn as_any(&self) -> &dyn Any { self }
+    fn evaluate(&self, _input: &RecordBatch) -> Result<ColumnValue> {
+        Err(ErrorCode::NotSupported(format!("{:?} with arguments is evaluated on the device only (nqe_expr_evaluate)", self.func)))
+    }
+}
+
 fn zero_node() -> NqeExprNode { NqeExprNode { kind: 0, op: 0, column: 0, dtype: 0, is_null: 0, utf8_length: 0, value: NqeValue { i64_: 0 } } }
 
 /// ColumnExpr → column index: prefer idx, else the FIRST field with that name (column.rs:39-57, quirk Q12)
@@ -420,6 +436,10 @@ fn flatten(e: &PhysicalExprRef, schema: &NaiveSchema, out: &mut Vec<NqeExprNode>
     } else if let Some(s) = e.as_any().downcast_ref::<PhysicalStringExpr>() {
         flatten(&s.expr, schema, out, keep)?;
         out.push(NqeExprNode { kind: NQE_EXPR_STRING, op: s.func.clone() as i32, ..zero_node() });
+    } else if let Some(s) = e.as_any().downcast_ref::<PhysicalStringArgsExpr>() {
+        flatten(&s.expr, schema, out, keep)?; // post-order, children left to right: the string deepest, the last argument on top
+        for a in s.args.iter() { flatten(a, schema, out, keep)?; }
+        out.push(NqeExprNode { kind: NQE_EXPR_STRING_ARGS, op: s.func.clone() as i32, ..zero_node() });
     } else {
         return Err(ErrorCode::NotSupported("expression kind has no device implementation (cast)".to_string()));
     }

@@ -6,6 +6,7 @@
 
 #include "device_utils.hpp"
 #include "nqe_internal.hpp"
+#include "string_lanes.hpp"
 
 void AggSwitches::read_environment() {
     const char *e = getenv("NQE_TINY_UNPACK_TILES");
@@ -408,11 +409,8 @@ DevColumn take_utf8(nqe_ctx *ctx, const DevColumn &src, const int64_t *idx, int6
     out.data_length = total;
     out.data = dev_alloc(ctx, size_t(total) + 8);
     if (m && total) {
-        const uint64_t mean = uint64_t(total) / uint64_t(m);
-        const int lg = mean <= 32 ? 2 : mean <= 96 ? 3 : mean <= 256 ? 4 : mean <= 1024 ? 5 : 6; // lanes per string (a lane moves 8 bytes per step)
-        auto k = lg == 2 ? utf8_take_copy_kernel<2> : lg == 3 ? utf8_take_copy_kernel<3> : lg == 4 ? utf8_take_copy_kernel<4> : lg == 5 ? utf8_take_copy_kernel<5>
-                                                                                                                                     : utf8_take_copy_kernel<6>;
-        launch(ctx, "utf8_take_copy", k, dim3(stream_grid(ctx, (m + (64 >> lg) - 1) / (64 >> lg), 4)), dim3(256), 0, (const int32_t *)src.values->ptr,
+        const int lg = lanes_log2(total, m);
+        launch(ctx, "utf8_take_copy", NQE_STR_PICK(utf8_take_copy_kernel, lg), dim3(group_grid(ctx, m, lg)), dim3(256), 0, (const int32_t *)src.values->ptr,
                src.data ? (const uint8_t *)src.data->ptr : nullptr, src.valid(), src.length, idx, m, (const uint32_t *)out.values->ptr,
                (uint8_t *)out.data->ptr);
     }

@@ -122,6 +122,19 @@ Value eval_node(nqe_ctx *ctx, const nqe_table *in, const std::vector<Node> &t, i
         v.col = string_fn(ctx, x.op, c.col);
         return v;
     }
+    if (x.kind == NQE_EXPR_STRING_ARGS) { // quirk Q26 (string_args.hip): Utf8; NULL where any operand is
+        Value s = eval_node(ctx, in, t, x.left);
+        if (s.is_lit) s.col = utf8_literal_column(ctx, s.lit_str, s.lit_null, in->rows);
+        Value a = eval_node(ctx, in, t, x.right), b;
+        if (x.third >= 0) b = eval_node(ctx, in, t, x.third);
+        if (x.op == NQE_UNARY_REPLACE) { // parse: both are Utf8 literals
+            v.col = string_replace(ctx, s.col, a.lit_str, a.lit_null, b.lit_str, b.lit_null);
+            return v;
+        }
+        auto int_arg = [](const Value &k) { return k.is_lit ? StrIntArg{nullptr, int64_t(k.lit), k.lit_null} : StrIntArg{&k.col, 0, false}; };
+        v.col = x.op == NQE_UNARY_SUBSTR ? string_substr(ctx, s.col, int_arg(a), int_arg(b)) : string_repeat(ctx, s.col, int_arg(a));
+        return v;
+    }
     Value l = eval_node(ctx, in, t, x.left);
     Value r = eval_node(ctx, in, t, x.right);
     const int64_t n = in->rows;

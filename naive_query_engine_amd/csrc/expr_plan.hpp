@@ -38,13 +38,15 @@ struct Node {
     uint64_t lit = 0;
     std::string lit_str;       // Utf8 literal
     int left = -1, right = -1; // children (indices into the node vector); a UNARY node's operand is `left`
+    int third = -1;            // a STRING_ARGS node's last argument (SUBSTR's len, REPLACE's to): left = s, right = the first argument
     int out_dtype = NQE_NULLTYPE;
 };
 
 bool is_compare(int op) { return op >= NQE_OP_EQ && op <= NQE_OP_GT_EQ; }
 bool is_logic(int op) { return op == NQE_OP_AND || op == NQE_OP_OR; }
 bool is_arith(int op) { return op >= NQE_OP_PLUS && op <= NQE_OP_MODULOS; }
-bool is_op_node(int kind) { return kind == NQE_EXPR_BINARY || kind == NQE_EXPR_UNARY || kind == NQE_EXPR_STRING; } // a node with operands: a step of a program
+bool is_string_node(int kind) { return kind == NQE_EXPR_STRING || kind == NQE_EXPR_STRING_ARGS; } // Q25 and Q26: evaluated node at a time
+bool is_op_node(int kind) { return kind == NQE_EXPR_BINARY || kind == NQE_EXPR_UNARY || is_string_node(kind); } // a node with operands: a step of a program
 
 // ------------------------------------------------------------------ fused whole-tree evaluation: the stack machine's program
 // One instruction per BINARY or UNARY node (post-order), whose operands are a literal, a column word (slot k of the program's distinct
@@ -179,6 +181,26 @@ std::vector<Node> parse(const ExprView &in, const nqe_expr_node *nodes, int n, i
                 fail(NQE_ERR_NOT_SUPPORTED, "repeat / replace / substr need arguments a one-operand node cannot carry");
             if (t[size_t(x.left)].out_dtype != NQE_UTF8) fail(NQE_ERR_NOT_SUPPORTED, "a string function over an operand that is not Utf8");
             x.out_dtype = x.op == NQE_UNARY_CHARACTER_LENGTH ? NQE_INT64 : NQE_UTF8;
+        } else if (nd.kind == NQE_EXPR_STRING_ARGS) { // quirk Q26: substr / repeat / replace (string_args.hip)
+            x.op = nd.op;
+            if (x.op < NQE_UNARY_ABS || x.op > NQE_UNARY_SUBSTR) fail(NQE_ERR_INVALID_ARGUMENT, "unknown string function");
+            if (x.op != NQE_UNARY_REPEAT && x.op != NQE_UNARY_REPLACE && x.op != NQE_UNARY_SUBSTR)
+                fail(NQE_ERR_INVALID_ARGUMENT, "a function without arguments under a string-arguments node (it belongs under NQE_EXPR_UNARY or NQE_EXPR_STRING)");
+            const size_t pops = x.op == NQE_UNARY_REPEAT ? 2 : 3;
+            if (st.size() < pops) fail(NQE_ERR_INVALID_ARGUMENT, "malformed expression");
+            if (pops == 3) { x.third = st.back(); st.pop_back(); }
+            x.right = st.back(); st.pop_back();
+            x.left = st.back(); st.pop_back();
+            if (t[size_t(x.left)].out_dtype != NQE_UTF8) fail(NQE_ERR_NOT_SUPPORTED, "a string function over an operand that is not Utf8");
+            for (int a : {x.right, x.third}) {
+                if (a < 0) continue;
+                const Node &arg = t[size_t(a)];
+                if (x.op == NQE_UNARY_REPLACE) {
+                    if (arg.kind != NQE_EXPR_LITERAL || arg.dtype != NQE_UTF8) fail(NQE_ERR_NOT_SUPPORTED, "replace takes Utf8 literals for `from` and `to`");
+                } else if (arg.out_dtype != NQE_INT64)
+                    fail(NQE_ERR_NOT_SUPPORTED, "substr / repeat take Int64 arguments");
+            }
+            x.out_dtype = NQE_UTF8;
         } else {
             fail(NQE_ERR_INVALID_ARGUMENT, "unknown expression node kind");
         }
@@ -278,7 +300,7 @@ bool build_program(const ExprView &in, const std::vector<Node> &t, int root, ExP
         st.pop_back();
         const Node &x = t[size_t(i)];
         if (!is_op_node(x.kind)) continue;
-        if (x.kind == NQE_EXPR_STRING) return false; // the machine works on 8-byte words: a tree with a string step anywhere goes node at a time
+        if (is_string_node(x.kind)) return false; // the machine works on 8-byte words: a tree with a string step anywhere goes node at a time
         if (done) { order.push_back(i); continue; }
         st.push_back({i, true});
         if (x.kind == NQE_EXPR_BINARY) st.push_back({x.right, false});
@@ -457,7 +479,7 @@ bool match_conj(const ExprView &in, const nqe_expr_node *nodes, int n, ConjPred 
     // first node of the subtree that ends at node i
     int start[MAXN], stack[MAXN], sp = 0;
     for (int i = 0; i < n; ++i) {
-        if (nodes[i].kind == NQE_EXPR_UNARY || nodes[i].kind == NQE_EXPR_STRING) return false; // (a test is `col [arith lit] cmp lit`: no one-operand step; such trees go through expr_tree_kernel, or node at a time)
+        if (nodes[i].kind == NQE_EXPR_UNARY || is_string_node(nodes[i].kind)) return false; // (a test is `col [arith lit] cmp lit`: no one-operand step; such trees go through expr_tree_kernel, or node at a time)
         if (nodes[i].kind == NQE_EXPR_BINARY) {
             if (sp < 2) return false;
             sp -= 2;

@@ -331,6 +331,21 @@ DevColumn utf8_literal_column(nqe_ctx *ctx, const std::string &lit, bool lit_nul
 // string_fn.hip: one string function of an NQE_EXPR_STRING node (`op`: TRIM, LTRIM, RTRIM, CHARACTER_LENGTH, LOWER, UPPER or REVERSE of
 // nqe_unary_operator, checked by the parser) over the Utf8 column `src`; Utf8, or Int64 for CHARACTER_LENGTH, with src's validity
 DevColumn string_fn(nqe_ctx *ctx, int op, const DevColumn &src);
+// (string_fn.hip) the operand's validity as the result's — shared (reference-counted) when an output may alias it, else copied — with its
+// null_count; the operand's offsets as the result's, shared or copied likewise; a well-formed Utf8 column of no rows
+void carry_validity(nqe_ctx *ctx, const DevColumn &src, DevColumn *out);
+BufRef carry_offsets(nqe_ctx *ctx, const DevColumn &src);
+DevColumn empty_utf8(nqe_ctx *ctx);
+// string_args.hip: one function of an NQE_EXPR_STRING_ARGS node (quirk Q26) over the Utf8 column `src`.  An Int64 argument is a column
+// or a literal (`col` null: `lit`, `lit_null`); REPLACE's `from` and `to` are Utf8 literals.
+struct StrIntArg {
+    const DevColumn *col = nullptr;
+    int64_t lit = 0;
+    bool lit_null = false;
+};
+DevColumn string_substr(nqe_ctx *ctx, const DevColumn &src, const StrIntArg &start, const StrIntArg &len);
+DevColumn string_repeat(nqe_ctx *ctx, const DevColumn &src, const StrIntArg &n);
+DevColumn string_replace(nqe_ctx *ctx, const DevColumn &src, const std::string &from, bool from_null, const std::string &to, bool to_null);
 // general tree `nodes` over the rows of `km`, compacted in the same pass; false = does not fit the stack machine
 bool evaluate_expr_compacted(nqe_ctx *ctx, const nqe_table *in, const nqe_expr_node *nodes, int n, const KeepMask &km, DevColumn *result);
 // the whole projection list behind a selection in ONE run-time specialised kernel (expr_jit.hpp); false when the list does not fit it

@@ -8,18 +8,9 @@
 #include "device_utils.hpp"
 #include "nqe_internal.hpp"
 #include "string_fn_kernels.hpp"
+#include "string_lanes.hpp"
 
 namespace nqe {
-
-namespace {
-
-// lanes per string from the mean length, as take_utf8 picks them (a lane moves 8 bytes per step)
-int lanes_log2(int64_t bytes, int64_t rows) {
-    const uint64_t mean = uint64_t(bytes) / uint64_t(rows);
-    return mean <= 32 ? 2 : mean <= 96 ? 3 : mean <= 256 ? 4 : mean <= 1024 ? 5 : 6;
-}
-int group_grid(nqe_ctx *ctx, int64_t rows, int lg) { return stream_grid(ctx, (rows + (64 >> lg) - 1) / (64 >> lg), 4); }
-#define NQE_STR_PICK(kernel, lg) ((lg) == 2 ? kernel<2> : (lg) == 3 ? kernel<3> : (lg) == 4 ? kernel<4> : (lg) == 5 ? kernel<5> : kernel<6>)
 
 // the operand's validity as the result's: shared (reference-counted) when an output may alias it, else copied — what the unary node does
 void carry_validity(nqe_ctx *ctx, const DevColumn &src, DevColumn *out) {
@@ -48,8 +39,6 @@ DevColumn empty_utf8(nqe_ctx *ctx) {
     c.data = dev_alloc(ctx, 8);
     return c;
 }
-
-} // namespace
 
 DevColumn string_fn(nqe_ctx *ctx, int op, const DevColumn &src) {
     const int64_t n = src.length, bytes = src.data_length;

@@ -15,7 +15,7 @@ from __future__ import annotations
 from typing import List, Optional, Sequence
 
 from .arrow_host import (ErrorCode, Field, NqeExprNode, Operator, ScalarValue, Status, UnaryOperator, node_binary, node_column,
-                         node_literal, node_string, node_unary)
+                         node_literal, node_string, node_string_args, node_unary)
 
 
 class PhysicalExpr:
@@ -136,6 +136,33 @@ class PhysicalStringExpr(PhysicalExpr):
         return f"{self.func.name}({self.expr!r})"
 
 
+INT64_MAX = (1 << 63) - 1
+STRING_ARGS_FUNCTIONS = (UnaryOperator.Repeat, UnaryOperator.Replace, UnaryOperator.Substr)
+
+
+class PhysicalStringArgsExpr(PhysicalExpr):
+    """This package's own node beside the reference's (quirk Q26): the three functions of `enum UnaryOperator` that take arguments —
+    Substr(s, start, len), Repeat(s, n), Replace(s, from, to) — with a body, over a Utf8 operand `expr` and the argument expressions
+    `args` (Int64-valued for Substr and Repeat, Utf8 literals for Replace).  Any UnaryOperator and any number of arguments are taken
+    here and encoded as they are: the library refuses the others, as it refuses everything else about an expression."""
+
+    def __init__(self, func: UnaryOperator, expr: PhysicalExpr, args: Sequence[PhysicalExpr]):
+        self.func, self.expr, self.args = UnaryOperator(func), expr, list(args)
+
+    @staticmethod
+    def create(func: UnaryOperator, expr: PhysicalExpr, args: Sequence[PhysicalExpr]) -> "PhysicalStringArgsExpr":
+        return PhysicalStringArgsExpr(func, expr, args)
+
+    def flatten(self, fields):
+        out = self.expr.flatten(fields)  # post-order, children left to right: the string deepest, the last argument on top
+        for a in self.args:
+            out = out + a.flatten(fields)
+        return out + [node_string_args(self.func)]
+
+    def __repr__(self):
+        return f"{self.func.name}({', '.join(repr(e) for e in [self.expr] + self.args)})"
+
+
 # small conveniences for tests / bench (not part of the reference surface)
 def col(i_or_name) -> ColumnExpr:
     return ColumnExpr.try_create(None, i_or_name) if isinstance(i_or_name, int) else ColumnExpr.try_create(i_or_name, None)
@@ -171,3 +198,24 @@ def unop(func, e) -> PhysicalUnaryExpr:
 
 def strop(func, e) -> PhysicalStringExpr:
     return PhysicalStringExpr.create(e, func)
+
+
+def _int_arg(v) -> PhysicalExpr:
+    return v if isinstance(v, PhysicalExpr) else lit_i64(v)
+
+
+def _utf8_arg(v) -> PhysicalExpr:
+    return v if isinstance(v, PhysicalExpr) else lit_utf8(v)
+
+
+def substr(e, start, length=None) -> PhysicalStringArgsExpr:
+    """substr(e, start, length); length None: to the end (Int64 max — the node has no two-operand form)"""
+    return PhysicalStringArgsExpr.create(UnaryOperator.Substr, e, [_int_arg(start), _int_arg(INT64_MAX if length is None else length)])
+
+
+def repeat(e, n) -> PhysicalStringArgsExpr:
+    return PhysicalStringArgsExpr.create(UnaryOperator.Repeat, e, [_int_arg(n)])
+
+
+def replace(e, frm, to) -> PhysicalStringArgsExpr:
+    return PhysicalStringArgsExpr.create(UnaryOperator.Replace, e, [_utf8_arg(frm), _utf8_arg(to)])

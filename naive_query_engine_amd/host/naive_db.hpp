@@ -324,6 +324,28 @@ struct PhysicalStringExpr : PhysicalExpr {
     }
 };
 
+// This mirror's own node beside the reference's (quirk Q26): Substr(s, start, len), Repeat(s, n) or Replace(s, from, to) with a body, over a
+// Utf8 operand and its arguments (Int64-valued for Substr and Repeat, Utf8 literals for Replace); Utf8.  Flattened post-order, children
+// left to right: the string deepest, the last argument on top.
+struct PhysicalStringArgsExpr : PhysicalExpr {
+    UnaryOperator func;
+    PhysicalExprRef expr;
+    std::vector<PhysicalExprRef> args;
+    static PhysicalExprRef create(UnaryOperator func, PhysicalExprRef e, std::vector<PhysicalExprRef> args) {
+        auto s = std::make_shared<PhysicalStringArgsExpr>();
+        s->func = func; s->expr = std::move(e); s->args = std::move(args);
+        return s;
+    }
+    void flatten(const NaiveSchema &schema, std::vector<nqe_expr_node> &out) const override {
+        expr->flatten(schema, out);
+        for (const PhysicalExprRef &a : args) a->flatten(schema, out);
+        nqe_expr_node n{};
+        n.kind = NQE_EXPR_STRING_ARGS;
+        n.op = int32_t(func);
+        out.push_back(n);
+    }
+};
+
 // ---------------------------------------------------------------- datasource/memory.rs
 struct TableSource {
     virtual ~TableSource() = default;
@@ -1249,7 +1271,13 @@ struct WindowFunctionEx {
             else if (n.kind == NQE_EXPR_LITERAL) st.push_back(DataType(n.dtype));
             else if (n.kind == NQE_EXPR_UNARY && !st.empty()) st.back() = DataType::Float64;
             else if (n.kind == NQE_EXPR_STRING && !st.empty()) st.back() = n.op == NQE_UNARY_CHARACTER_LENGTH ? DataType::Int64 : DataType::Utf8; // quirk Q25
-            else if (n.kind == NQE_EXPR_BINARY && st.size() >= 2) {
+            else if (n.kind == NQE_EXPR_STRING_ARGS) { // quirk Q26: pops the string and its two (Repeat: one) arguments
+                const size_t pops = n.op == NQE_UNARY_REPEAT ? 2 : 3;
+                if (st.size() >= pops) {
+                    st.resize(st.size() - pops + 1);
+                    st.back() = DataType::Utf8;
+                }
+            } else if (n.kind == NQE_EXPR_BINARY && st.size() >= 2) {
                 st.pop_back();
                 if (n.op <= NQE_OP_GT_EQ || n.op >= NQE_OP_AND) st.back() = DataType::Boolean;
             }
