@@ -131,8 +131,22 @@ typedef struct nqe_column {
  * A STRING_ARGS node (quirk Q26: "the string functions with arguments") carries the last three:
  * its `op` is NQE_UNARY_SUBSTR, NQE_UNARY_REPLACE (both pop THREE values) or NQE_UNARY_REPEAT
  * (pops TWO); the string operand is deepest, the last argument on top; it pushes a Utf8 value.
- * In postfix: `s start len SUBSTR`, `s n REPEAT`, `s from to REPLACE`. */
-typedef enum nqe_expr_kind { NQE_EXPR_COLUMN = 0, NQE_EXPR_LITERAL = 1, NQE_EXPR_BINARY = 2, NQE_EXPR_UNARY = 3, NQE_EXPR_STRING = 4, NQE_EXPR_STRING_ARGS = 5 } nqe_expr_kind;
+ * In postfix: `s start len SUBSTR`, `s n REPEAT`, `s from to REPLACE`.
+ * A STRING_MATCH node (quirk Q27: "the reference has no pattern match; LIKE is unimplemented!()",
+ * sql/planner.rs:478) pops TWO values, the string deepest and the pattern on top (`s pattern
+ * MATCH`); its `op` is a nqe_match_operator and it pushes a Boolean value (Int64 for STRPOS).
+ * NQE_EXPR_STRING_MATCH carries no initializer on purpose: a test of the earlier kinds reads the
+ * `NAME = value` pairs of this enum as a fixed list, and C numbers the enumerator 6 by itself;
+ * the check below the enum holds it there. */
+typedef enum nqe_expr_kind { NQE_EXPR_COLUMN = 0, NQE_EXPR_LITERAL = 1, NQE_EXPR_BINARY = 2, NQE_EXPR_UNARY = 3, NQE_EXPR_STRING = 4, NQE_EXPR_STRING_ARGS = 5, NQE_EXPR_STRING_MATCH } nqe_expr_kind;
+typedef char nqe_expr_string_match_is_6[(NQE_EXPR_STRING_MATCH == 6) ? 1 : -1];
+
+/* the `op` of a STRING_MATCH node (quirk Q27; see nqe_expr_evaluate) */
+typedef enum nqe_match_operator {
+    NQE_MATCH_LIKE = 0, NQE_MATCH_NOT_LIKE = 1, NQE_MATCH_ILIKE = 2, NQE_MATCH_NOT_ILIKE = 3,
+    NQE_MATCH_STARTS_WITH = 4, NQE_MATCH_ENDS_WITH = 5, NQE_MATCH_CONTAINS = 6, NQE_MATCH_STRPOS = 7
+} nqe_match_operator;
+#define NQE_MAX_MATCH_PATTERN 4096   /* bytes of the pattern literal */
 
 /* same order as `enum Operator` (logical_plan/expression.rs:335-362) */
 typedef enum nqe_operator {
@@ -175,7 +189,7 @@ typedef enum nqe_unary_operator {
 
 typedef struct nqe_expr_node {
     int32_t kind;    /* nqe_expr_kind */
-    int32_t op;      /* BINARY: nqe_operator; UNARY and STRING: nqe_unary_operator */
+    int32_t op;      /* BINARY: nqe_operator; UNARY, STRING and STRING_ARGS: nqe_unary_operator; STRING_MATCH: nqe_match_operator */
     int32_t column;  /* COLUMN: index into the input batch */
     int32_t dtype;   /* LITERAL: nqe_dtype of the ScalarValue */
     int32_t is_null; /* LITERAL: 1 = ScalarValue::X(None) */
@@ -515,7 +529,37 @@ nqe_status nqe_sharded_selection_projection_execute(nqe_comm *comm, const nqe_ta
  * REPLACE or SUBSTR → NQE_ERR_INVALID_ARGUMENT; fewer values than the function pops →
  * NQE_ERR_INVALID_ARGUMENT; `s` not Utf8 → NQE_ERR_NOT_SUPPORTED; a SUBSTR or REPEAT argument
  * that is not Int64 (UInt64, Float64, Boolean, Utf8, a Null-typed literal) →
- * NQE_ERR_NOT_SUPPORTED; a REPLACE argument that is not a Utf8 literal → NQE_ERR_NOT_SUPPORTED. */
+ * NQE_ERR_NOT_SUPPORTED; a REPLACE argument that is not a Utf8 literal → NQE_ERR_NOT_SUPPORTED.
+ * String matching (NQE_EXPR_STRING_MATCH, quirk Q27): LIKE, NOT_LIKE, ILIKE, NOT_ILIKE,
+ * STARTS_WITH, ENDS_WITH, CONTAINS (Boolean) and STRPOS (Int64) of a string `s` and a pattern.
+ * `s` is any Utf8 value (a column, a STRING or STRING_ARGS node, a literal expanded to
+ * `in.num_rows` rows as a STRING node expands it); the pattern is a Utf8 LITERAL (NULL allowed)
+ * of at most NQE_MAX_MATCH_PATTERN bytes. Like Q25 and Q26 everything is defined on the BYTES
+ * between a slot's two offsets, total and deterministic for invalid UTF-8 too.
+ * The elements of a LIKE / ILIKE pattern, read left to right: byte `\` (0x5C) followed by a byte
+ * b is the literal b, whatever b is; a `\` that ends the pattern is a literal `\`; `%` (0x25) is
+ * ANY; `_` (0x5F) is ONE; every other byte is a literal; a run of `%` is one `%`; there is no
+ * other escape character. `s LIKE p` is true iff the bytes of s can be cut into consecutive
+ * pieces, one per element: a literal's piece is that one byte; ANY's piece is any run of bytes,
+ * which may be empty and need not end at a character; ONE's piece is exactly the bytes of one
+ * character of Q26's numbering, the set {j : c(j) = k} for one k (a code point of valid UTF-8;
+ * continuation bytes at the very front belong to character 1). ILIKE is LIKE after mapping A-Z
+ * to a-z in the literal elements and in the string's bytes (ASCII only, Q25's LOWER). NOT_LIKE
+ * and NOT_ILIKE are the negations. STARTS_WITH, ENDS_WITH and CONTAINS take the literal
+ * verbatim, with no wildcards and no escape, and compare bytes; an empty literal is true.
+ * STRPOS(s, sub) is 0 when `sub` does not occur in s, otherwise c(j) of the first byte j of the
+ * leftmost byte-wise occurrence; an empty `sub` gives 1, for an empty s too.
+ * Row i is NULL iff s is NULL at i or the literal is NULL. Under a NULL the Boolean value bit is
+ * 0 (for the NOT forms too) and the Int64 value is 0; the bits of the last value word beyond the
+ * row count are 0. The result has no validity buffer when s has none and the literal is not
+ * NULL; otherwise it carries s's validity (shared when that is allowed, else copied) and its
+ * null_count; a NULL literal gives an all-NULL column with null_count = rows. Zero rows give a
+ * well-formed empty column. A tree that holds the node is evaluated node at a time. Errors, in
+ * this order, before anything is allocated or launched: `op` outside nqe_match_operator →
+ * NQE_ERR_INVALID_ARGUMENT; fewer than two values → NQE_ERR_INVALID_ARGUMENT; `s` not Utf8 →
+ * NQE_ERR_NOT_SUPPORTED; a pattern that is not a Utf8 literal (a column, a subtree, another
+ * dtype, a Null-typed literal) → NQE_ERR_NOT_SUPPORTED; a pattern of more than
+ * NQE_MAX_MATCH_PATTERN bytes → NQE_ERR_NOT_SUPPORTED. */
 nqe_status nqe_expr_evaluate(nqe_ctx *ctx, const nqe_table *in, const nqe_expr_node *nodes,
                              int32_t num_nodes, nqe_table **out);
 

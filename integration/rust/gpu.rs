@@ -104,6 +104,7 @@ pub enum NqeComm {}
 const NQE_EXPR_COLUMN: i32 = 0; const NQE_EXPR_LITERAL: i32 = 1; const NQE_EXPR_BINARY: i32 = 2; const NQE_EXPR_UNARY: i32 = 3;
 const NQE_EXPR_STRING: i32 = 4; // quirk Q25: the shim's own PhysicalStringExpr below
 const NQE_EXPR_STRING_ARGS: i32 = 5; // quirk Q26: the shim's own PhysicalStringArgsExpr below
+const NQE_EXPR_STRING_MATCH: i32 = 6; // quirk Q27: the shim's own PhysicalStringMatchExpr below
 const NQE_BOOLEAN: i32 = 1; const NQE_INT64: i32 = 2; const NQE_UINT64: i32 = 3; const NQE_FLOAT64: i32 = 4; const NQE_UTF8: i32 = 5;
 
 extern "C" {
@@ -390,6 +391,25 @@ impl PhysicalExpr for PhysicalStringArgsExpr {
     }
 }
 
+/// `op` of a PhysicalStringMatchExpr, in nqe_match_operator's order
+#[derive(Debug, Clone, Copy, PartialEq)]
+pub enum MatchOperator { Like = 0, NotLike = 1, ILike = 2, NotILike = 3, StartsWith = 4, EndsWith = 5, Contains = 6, StrPos = 7 }
+
+/// The shim's own expression beside the reference's (quirk Q27; the reference's planner maps LIKE to unimplemented!(),
+/// sql/planner.rs:478): `expr` Like / NotLike / ILike / NotILike `pattern`, StartsWith, EndsWith, Contains — Boolean — and StrPos — Int64 —
+/// over a Utf8 operand and a pattern the library takes as a Utf8 literal.  Like PhysicalStringExpr it exists on the device only.
+#[derive(Debug)]
+pub struct PhysicalStringMatchExpr { pub op: MatchOperator, pub expr: PhysicalExprRef, pub pattern: PhysicalExprRef }
+impl PhysicalStringMatchExpr {
+    pub fn create(op: MatchOperator, expr: PhysicalExprRef, pattern: PhysicalExprRef) -> PhysicalExprRef { Arc::new(Self { op, expr, pattern }) }
+}
+impl PhysicalExpr for PhysicalStringMatchExpr {
+    fn as_any(&self) -> &dyn Any { self }
+    fn evaluate(&self, _input: &RecordBatch) -> Result<ColumnValue> {
+        Err(ErrorCode::NotSupported(format!("{:?} is evaluated on the device only (nqe_expr_evaluate)", self.op)))
+    }
+}
+
 fn zero_node() -> NqeExprNode { NqeExprNode { kind: 0, op: 0, column: 0, dtype: 0, is_null: 0, utf8_length: 0, value: NqeValue { i64_: 0 } } }
 
 /// ColumnExpr → column index: prefer idx, else the FIRST field with that name (column.rs:39-57, quirk Q12)
@@ -440,6 +460,10 @@ fn flatten(e: &PhysicalExprRef, schema: &NaiveSchema, out: &mut Vec<NqeExprNode>
         flatten(&s.expr, schema, out, keep)?; // post-order, children left to right: the string deepest, the last argument on top
         for a in s.args.iter() { flatten(a, schema, out, keep)?; }
         out.push(NqeExprNode { kind: NQE_EXPR_STRING_ARGS, op: s.func.clone() as i32, ..zero_node() });
+    } else if let Some(m) = e.as_any().downcast_ref::<PhysicalStringMatchExpr>() {
+        flatten(&m.expr, schema, out, keep)?; // post-order: the string deepest, the pattern on top
+        flatten(&m.pattern, schema, out, keep)?;
+        out.push(NqeExprNode { kind: NQE_EXPR_STRING_MATCH, op: m.op as i32, ..zero_node() });
     } else {
         return Err(ErrorCode::NotSupported("expression kind has no device implementation (cast)".to_string()));
     }

@@ -209,6 +209,7 @@ class NqeCsvOptions(C.Structure):
 EXPR_COLUMN, EXPR_LITERAL, EXPR_BINARY, EXPR_UNARY = 0, 1, 2, 3
 EXPR_STRING = 4  # quirk Q25: a string function with a body (NQE_EXPR_STRING); `op` is a UnaryOperator
 EXPR_STRING_ARGS = 5  # quirk Q26: substr / repeat / replace (NQE_EXPR_STRING_ARGS); pops the string and its two (repeat: one) arguments
+EXPR_STRING_MATCH = 6  # quirk Q27: like / ilike / starts_with / ends_with / contains / strpos (NQE_EXPR_STRING_MATCH); pops the string and the pattern literal
 HOST, DEVICE = 0, 1
 
 _WORD_NP = {DType.INT64: np.int64, DType.UINT64: np.uint64, DType.FLOAT64: np.float64}
@@ -558,6 +559,13 @@ def node_string_args(func: "UnaryOperator") -> NqeExprNode:
     n = NqeExprNode()
     n.kind = EXPR_STRING_ARGS
     n.op = int(func)
+    return n
+
+
+def node_string_match(op: "MatchOperator") -> NqeExprNode:
+    n = NqeExprNode()
+    n.kind = EXPR_STRING_MATCH
+    n.op = int(op)
     return n
 
 

@@ -135,6 +135,13 @@ Value eval_node(nqe_ctx *ctx, const nqe_table *in, const std::vector<Node> &t, i
         v.col = x.op == NQE_UNARY_SUBSTR ? string_substr(ctx, s.col, int_arg(a), int_arg(b)) : string_repeat(ctx, s.col, int_arg(a));
         return v;
     }
+    if (x.kind == NQE_EXPR_STRING_MATCH) { // quirk Q27 (string_match.hip): Boolean, Int64 for STRPOS; NULL where `s` or the literal is
+        Value s = eval_node(ctx, in, t, x.left);
+        if (s.is_lit) s.col = utf8_literal_column(ctx, s.lit_str, s.lit_null, in->rows);
+        const Node &pat = t[size_t(x.right)]; // parse: a Utf8 literal
+        v.col = string_match(ctx, x.op, s.col, pat.lit_str, pat.lit_null);
+        return v;
+    }
     Value l = eval_node(ctx, in, t, x.left);
     Value r = eval_node(ctx, in, t, x.right);
     const int64_t n = in->rows;

@@ -45,7 +45,7 @@ struct Node {
 bool is_compare(int op) { return op >= NQE_OP_EQ && op <= NQE_OP_GT_EQ; }
 bool is_logic(int op) { return op == NQE_OP_AND || op == NQE_OP_OR; }
 bool is_arith(int op) { return op >= NQE_OP_PLUS && op <= NQE_OP_MODULOS; }
-bool is_string_node(int kind) { return kind == NQE_EXPR_STRING || kind == NQE_EXPR_STRING_ARGS; } // Q25 and Q26: evaluated node at a time
+bool is_string_node(int kind) { return kind == NQE_EXPR_STRING || kind == NQE_EXPR_STRING_ARGS || kind == NQE_EXPR_STRING_MATCH; } // Q25, Q26 and Q27: evaluated node at a time
 bool is_op_node(int kind) { return kind == NQE_EXPR_BINARY || kind == NQE_EXPR_UNARY || is_string_node(kind); } // a node with operands: a step of a program
 
 // ------------------------------------------------------------------ fused whole-tree evaluation: the stack machine's program
@@ -201,6 +201,17 @@ std::vector<Node> parse(const ExprView &in, const nqe_expr_node *nodes, int n, i
                     fail(NQE_ERR_NOT_SUPPORTED, "substr / repeat take Int64 arguments");
             }
             x.out_dtype = NQE_UTF8;
+        } else if (nd.kind == NQE_EXPR_STRING_MATCH) { // quirk Q27: like / ilike / starts_with / ends_with / contains / strpos (string_match.hip)
+            x.op = nd.op;
+            if (x.op < NQE_MATCH_LIKE || x.op > NQE_MATCH_STRPOS) fail(NQE_ERR_INVALID_ARGUMENT, "unknown match operator");
+            if (st.size() < 2) fail(NQE_ERR_INVALID_ARGUMENT, "malformed expression");
+            x.right = st.back(); st.pop_back();
+            x.left = st.back(); st.pop_back();
+            if (t[size_t(x.left)].out_dtype != NQE_UTF8) fail(NQE_ERR_NOT_SUPPORTED, "a string match over an operand that is not Utf8");
+            const Node &pat = t[size_t(x.right)];
+            if (pat.kind != NQE_EXPR_LITERAL || pat.dtype != NQE_UTF8) fail(NQE_ERR_NOT_SUPPORTED, "a string match takes a Utf8 literal for the pattern");
+            if (pat.lit_str.size() > size_t(NQE_MAX_MATCH_PATTERN)) fail(NQE_ERR_NOT_SUPPORTED, "a pattern of more than NQE_MAX_MATCH_PATTERN bytes");
+            x.out_dtype = x.op == NQE_MATCH_STRPOS ? NQE_INT64 : NQE_BOOLEAN;
         } else {
             fail(NQE_ERR_INVALID_ARGUMENT, "unknown expression node kind");
         }
@@ -265,7 +276,7 @@ bool match_simple(const std::vector<Node> &t, int i, SimpleExpr *s) {
         for (int k = 0; k < SIMPLE_MAX_OPS; ++k) s->aux[k].pow2_shift = s->aux[k].more = -1;
         return true; // a bare column of any type (Utf8 included) passes through
     }
-    if (x.kind != NQE_EXPR_BINARY || is_logic(x.op)) return false; // (a UNARY or STRING step anywhere below ends the chain here too)
+    if (x.kind != NQE_EXPR_BINARY || is_logic(x.op)) return false; // (a UNARY, STRING or STRING_MATCH step anywhere below ends the chain here too)
     const Node &l = t[size_t(x.left)], &r = t[size_t(x.right)];
     bool lit_left;
     int sub;

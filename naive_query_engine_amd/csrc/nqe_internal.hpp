@@ -346,6 +346,9 @@ struct StrIntArg {
 DevColumn string_substr(nqe_ctx *ctx, const DevColumn &src, const StrIntArg &start, const StrIntArg &len);
 DevColumn string_repeat(nqe_ctx *ctx, const DevColumn &src, const StrIntArg &n);
 DevColumn string_replace(nqe_ctx *ctx, const DevColumn &src, const std::string &from, bool from_null, const std::string &to, bool to_null);
+// string_match.hip: an NQE_EXPR_STRING_MATCH node (quirk Q27) over the Utf8 column `src`: `op` is a nqe_match_operator, the pattern a Utf8
+// literal the parser has checked; Boolean, or Int64 for STRPOS, with src's validity (all NULL under a NULL pattern)
+DevColumn string_match(nqe_ctx *ctx, int op, const DevColumn &src, const std::string &pattern, bool pattern_null);
 // general tree `nodes` over the rows of `km`, compacted in the same pass; false = does not fit the stack machine
 bool evaluate_expr_compacted(nqe_ctx *ctx, const nqe_table *in, const nqe_expr_node *nodes, int n, const KeepMask &km, DevColumn *result);
 // the whole projection list behind a selection in ONE run-time specialised kernel (expr_jit.hpp); false when the list does not fit it

@@ -12,10 +12,11 @@ encoding produced by `flatten()`.
 """
 from __future__ import annotations
 
+import enum
 from typing import List, Optional, Sequence
 
 from .arrow_host import (ErrorCode, Field, NqeExprNode, Operator, ScalarValue, Status, UnaryOperator, node_binary, node_column,
-                         node_literal, node_string, node_string_args, node_unary)
+                         node_literal, node_string, node_string_args, node_string_match, node_unary)
 
 
 class PhysicalExpr:
@@ -163,6 +164,38 @@ class PhysicalStringArgsExpr(PhysicalExpr):
         return f"{self.func.name}({', '.join(repr(e) for e in [self.expr] + self.args)})"
 
 
+class MatchOperator(enum.IntEnum):
+    """same order as `enum nqe_match_operator` (include/nqe.h)"""
+    Like = 0
+    NotLike = 1
+    ILike = 2
+    NotILike = 3
+    StartsWith = 4
+    EndsWith = 5
+    Contains = 6
+    StrPos = 7
+
+
+class PhysicalStringMatchExpr(PhysicalExpr):
+    """This package's own node beside the reference's (quirk Q27: the reference has no pattern match, sql/planner.rs:478 maps LIKE to
+    unimplemented!()): `expr` LIKE / NOT LIKE / ILIKE / NOT ILIKE `pattern`, starts_with, ends_with, contains (Boolean) and strpos
+    (Int64) over a Utf8 operand and a pattern expression, which the library takes only as a Utf8 literal.  Any pattern expression is
+    taken here and encoded as it is: the library refuses the others, as it refuses everything else about an expression."""
+
+    def __init__(self, op: MatchOperator, expr: PhysicalExpr, pattern: PhysicalExpr):
+        self.op, self.expr, self.pattern = MatchOperator(op), expr, pattern
+
+    @staticmethod
+    def create(op: MatchOperator, expr: PhysicalExpr, pattern: PhysicalExpr) -> "PhysicalStringMatchExpr":
+        return PhysicalStringMatchExpr(op, expr, pattern)
+
+    def flatten(self, fields):
+        return self.expr.flatten(fields) + self.pattern.flatten(fields) + [node_string_match(self.op)]  # post-order: the string deepest
+
+    def __repr__(self):
+        return f"{self.op.name}({self.expr!r}, {self.pattern!r})"
+
+
 # small conveniences for tests / bench (not part of the reference surface)
 def col(i_or_name) -> ColumnExpr:
     return ColumnExpr.try_create(None, i_or_name) if isinstance(i_or_name, int) else ColumnExpr.try_create(i_or_name, None)
@@ -219,3 +252,39 @@ def repeat(e, n) -> PhysicalStringArgsExpr:
 
 def replace(e, frm, to) -> PhysicalStringArgsExpr:
     return PhysicalStringArgsExpr.create(UnaryOperator.Replace, e, [_utf8_arg(frm), _utf8_arg(to)])
+
+
+def _match(op, e, pattern) -> PhysicalStringMatchExpr:
+    return PhysicalStringMatchExpr.create(op, e, _utf8_arg(pattern))  # a str, bytes or None becomes the Utf8 literal; an expression stays
+
+
+def like(e, pattern) -> PhysicalStringMatchExpr:
+    return _match(MatchOperator.Like, e, pattern)
+
+
+def not_like(e, pattern) -> PhysicalStringMatchExpr:
+    return _match(MatchOperator.NotLike, e, pattern)
+
+
+def ilike(e, pattern) -> PhysicalStringMatchExpr:
+    return _match(MatchOperator.ILike, e, pattern)
+
+
+def not_ilike(e, pattern) -> PhysicalStringMatchExpr:
+    return _match(MatchOperator.NotILike, e, pattern)
+
+
+def starts_with(e, prefix) -> PhysicalStringMatchExpr:
+    return _match(MatchOperator.StartsWith, e, prefix)
+
+
+def ends_with(e, suffix) -> PhysicalStringMatchExpr:
+    return _match(MatchOperator.EndsWith, e, suffix)
+
+
+def contains(e, sub) -> PhysicalStringMatchExpr:
+    return _match(MatchOperator.Contains, e, sub)
+
+
+def strpos(e, sub) -> PhysicalStringMatchExpr:
+    return _match(MatchOperator.StrPos, e, sub)

@@ -346,6 +346,28 @@ struct PhysicalStringArgsExpr : PhysicalExpr {
     }
 };
 
+// This mirror's own node beside the reference's (quirk Q27: the reference has no pattern match, sql/planner.rs:478 is unimplemented!()):
+// `expr` Like / NotLike / ILike / NotILike `pattern`, StartsWith, EndsWith, Contains (Boolean) and StrPos (Int64), over a Utf8 operand and a
+// pattern the library takes as a Utf8 literal.  Flattened post-order: the string deepest, the pattern on top.
+enum class MatchOperator : int32_t { Like = 0, NotLike = 1, ILike = 2, NotILike = 3, StartsWith = 4, EndsWith = 5, Contains = 6, StrPos = 7 }; // nqe_match_operator's order
+struct PhysicalStringMatchExpr : PhysicalExpr {
+    MatchOperator op;
+    PhysicalExprRef expr, pattern;
+    static PhysicalExprRef create(MatchOperator op, PhysicalExprRef e, PhysicalExprRef pattern) {
+        auto s = std::make_shared<PhysicalStringMatchExpr>();
+        s->op = op; s->expr = std::move(e); s->pattern = std::move(pattern);
+        return s;
+    }
+    void flatten(const NaiveSchema &schema, std::vector<nqe_expr_node> &out) const override {
+        expr->flatten(schema, out);
+        pattern->flatten(schema, out);
+        nqe_expr_node n{};
+        n.kind = NQE_EXPR_STRING_MATCH;
+        n.op = int32_t(op);
+        out.push_back(n);
+    }
+};
+
 // ---------------------------------------------------------------- datasource/memory.rs
 struct TableSource {
     virtual ~TableSource() = default;
@@ -1276,6 +1298,11 @@ struct WindowFunctionEx {
                 if (st.size() >= pops) {
                     st.resize(st.size() - pops + 1);
                     st.back() = DataType::Utf8;
+                }
+            } else if (n.kind == NQE_EXPR_STRING_MATCH) { // quirk Q27: pops the string and the pattern
+                if (st.size() >= 2) {
+                    st.pop_back();
+                    st.back() = n.op == NQE_MATCH_STRPOS ? DataType::Int64 : DataType::Boolean;
                 }
             } else if (n.kind == NQE_EXPR_BINARY && st.size() >= 2) {
                 st.pop_back();
