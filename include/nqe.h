@@ -137,9 +137,25 @@ typedef struct nqe_column {
  * MATCH`); its `op` is a nqe_match_operator and it pushes a Boolean value (Int64 for STRPOS).
  * NQE_EXPR_STRING_MATCH carries no initializer on purpose: a test of the earlier kinds reads the
  * `NAME = value` pairs of this enum as a fixed list, and C numbers the enumerator 6 by itself;
- * the check below the enum holds it there. */
+ * the check below the enum holds it there.
+ * A CONDITIONAL node (quirk Q28: "conditional and NULL-handling expressions"; the reference's
+ * planner leaves IsNull, Not and Case unimplemented!(), sql/planner.rs) is NQE_EXPR_CONDITIONAL
+ * = 7, a #define beside the enum for the same reason. Its `op` is a nqe_cond_operator and its
+ * `column` field carries the number of values it pops, which must be the function's arity:
+ * NOT, IS_NULL and IS_NOT_NULL pop ONE, COALESCE and NULLIF TWO, IF THREE (the condition deepest,
+ * the else value on top). In postfix: `b NOT`, `x IS_NULL`, `a b COALESCE`, `a b NULLIF`,
+ * `c t e IF`; coalesce(a, b, c) is `a b c COALESCE COALESCE`, CASE WHEN c1 THEN x WHEN c2 THEN y
+ * ELSE z END is `c1 x c2 y z IF IF`, and a CASE without ELSE takes a NULL literal as `e`. A
+ * reader of the flat encoding can walk the stack by `column` alone. */
 typedef enum nqe_expr_kind { NQE_EXPR_COLUMN = 0, NQE_EXPR_LITERAL = 1, NQE_EXPR_BINARY = 2, NQE_EXPR_UNARY = 3, NQE_EXPR_STRING = 4, NQE_EXPR_STRING_ARGS = 5, NQE_EXPR_STRING_MATCH } nqe_expr_kind;
 typedef char nqe_expr_string_match_is_6[(NQE_EXPR_STRING_MATCH == 6) ? 1 : -1];
+#define NQE_EXPR_CONDITIONAL 7
+typedef char nqe_expr_conditional_is_7[(NQE_EXPR_CONDITIONAL == NQE_EXPR_STRING_MATCH + 1) ? 1 : -1];
+
+/* the `op` of a CONDITIONAL node (quirk Q28; see nqe_expr_evaluate) */
+typedef enum nqe_cond_operator {
+    NQE_COND_NOT = 0, NQE_COND_IS_NULL = 1, NQE_COND_IS_NOT_NULL = 2, NQE_COND_COALESCE = 3, NQE_COND_NULLIF = 4, NQE_COND_IF = 5
+} nqe_cond_operator;
 
 /* the `op` of a STRING_MATCH node (quirk Q27; see nqe_expr_evaluate) */
 typedef enum nqe_match_operator {
@@ -189,8 +205,8 @@ typedef enum nqe_unary_operator {
 
 typedef struct nqe_expr_node {
     int32_t kind;    /* nqe_expr_kind */
-    int32_t op;      /* BINARY: nqe_operator; UNARY, STRING and STRING_ARGS: nqe_unary_operator; STRING_MATCH: nqe_match_operator */
-    int32_t column;  /* COLUMN: index into the input batch */
+    int32_t op;      /* BINARY: nqe_operator; UNARY, STRING and STRING_ARGS: nqe_unary_operator; STRING_MATCH: nqe_match_operator; CONDITIONAL: nqe_cond_operator */
+    int32_t column;  /* COLUMN: index into the input batch; CONDITIONAL: the number of values the node pops (its arity) */
     int32_t dtype;   /* LITERAL: nqe_dtype of the ScalarValue */
     int32_t is_null; /* LITERAL: 1 = ScalarValue::X(None) */
     int32_t utf8_length; /* LITERAL of dtype NQE_UTF8: byte length of value.utf8 (the field was `reserved` before Utf8
@@ -559,7 +575,33 @@ nqe_status nqe_sharded_selection_projection_execute(nqe_comm *comm, const nqe_ta
  * NQE_ERR_INVALID_ARGUMENT; fewer than two values → NQE_ERR_INVALID_ARGUMENT; `s` not Utf8 →
  * NQE_ERR_NOT_SUPPORTED; a pattern that is not a Utf8 literal (a column, a subtree, another
  * dtype, a Null-typed literal) → NQE_ERR_NOT_SUPPORTED; a pattern of more than
- * NQE_MAX_MATCH_PATTERN bytes → NQE_ERR_NOT_SUPPORTED. */
+ * NQE_MAX_MATCH_PATTERN bytes → NQE_ERR_NOT_SUPPORTED.
+ * Conditional and NULL-handling functions (NQE_EXPR_CONDITIONAL, quirk Q28): NOT(b), IS_NULL(x),
+ * IS_NOT_NULL(x), COALESCE(a, b), NULLIF(a, b) and IF(c, t, e). Every operand may be of any form:
+ * a column, a literal (a NULL literal included) or any subtree, string nodes and other
+ * CONDITIONAL nodes included; the value dtypes are Int64, UInt64, Float64, Boolean and Utf8.
+ * NOT is NULL where b is NULL. IS_NULL and IS_NOT_NULL read validity only and are never NULL.
+ * COALESCE is a where a is valid, else b (NULL where both are). IF is t where c is valid AND
+ * true, and e where c is false OR NULL (SQL CASE; a NULL condition is not propagated). NULLIF is
+ * by definition IF(a = b, NULL, a) with `=` this library's NQE_OP_EQ on that dtype: Int64, UInt64
+ * and Boolean compare their values; Float64 compares as IEEE does, so NaN equals nothing
+ * (NULLIF(NaN, NaN) is NaN) and -0.0 equals +0.0 (NULLIF(-0.0, 0.0) is NULL); Utf8 compares
+ * bytes; a NULL a or b makes a = b NULL, so the row is a. Under a NULL result row the word is 0,
+ * the Boolean bit is 0 and a Utf8 row is the empty string; the bits of the last value or
+ * validity word beyond the row count are 0. A result carries a validity buffer only where the
+ * static form can be NULL: NOT iff b can be (a nullable column, a NULL literal or a subtree
+ * whose result carries one), IS_NULL and IS_NOT_NULL never, COALESCE iff both operands can be,
+ * IF iff t or e can be, NULLIF always; with a buffer null_count is -1, without one 0. Zero rows
+ * give a well-formed column; an all-literal node is expanded to `in.num_rows` rows. A Utf8
+ * result of more than 2^31-1 bytes fails with NQE_ERR_ARROW ("offset overflow"): the total is
+ * computed in 64 bits, the failure comes before the data buffer is allocated, and the context
+ * stays usable. A tree that holds the node is evaluated node at a time. Errors, in this order,
+ * before anything is allocated or launched: `column` outside 1..3 → NQE_ERR_INVALID_ARGUMENT;
+ * `op` outside nqe_cond_operator → NQE_ERR_INVALID_ARGUMENT; `column` not the function's arity →
+ * NQE_ERR_INVALID_ARGUMENT; fewer values than the node pops → NQE_ERR_INVALID_ARGUMENT; an
+ * operand of dtype NQE_NULLTYPE → NQE_ERR_NOT_SUPPORTED; NOT's operand or IF's `c` not Boolean →
+ * NQE_ERR_INTERVAL; the two value operands of COALESCE, NULLIF or IF of different dtypes →
+ * NQE_ERR_INTERVAL. */
 nqe_status nqe_expr_evaluate(nqe_ctx *ctx, const nqe_table *in, const nqe_expr_node *nodes,
                              int32_t num_nodes, nqe_table **out);
 

@@ -105,6 +105,7 @@ const NQE_EXPR_COLUMN: i32 = 0; const NQE_EXPR_LITERAL: i32 = 1; const NQE_EXPR_
 const NQE_EXPR_STRING: i32 = 4; // quirk Q25: the shim's own PhysicalStringExpr below
 const NQE_EXPR_STRING_ARGS: i32 = 5; // quirk Q26: the shim's own PhysicalStringArgsExpr below
 const NQE_EXPR_STRING_MATCH: i32 = 6; // quirk Q27: the shim's own PhysicalStringMatchExpr below
+const NQE_EXPR_CONDITIONAL: i32 = 7; // quirk Q28: the shim's own PhysicalConditionalExpr below; the node's `column` carries the number of values it pops
 const NQE_BOOLEAN: i32 = 1; const NQE_INT64: i32 = 2; const NQE_UINT64: i32 = 3; const NQE_FLOAT64: i32 = 4; const NQE_UTF8: i32 = 5;
 
 extern "C" {
@@ -410,6 +411,25 @@ impl PhysicalExpr for PhysicalStringMatchExpr {
     }
 }
 
+/// `op` of a PhysicalConditionalExpr, in nqe_cond_operator's order
+#[derive(Debug, Clone, Copy, PartialEq)]
+pub enum CondOperator { Not = 0, IsNull = 1, IsNotNull = 2, Coalesce = 3, NullIf = 4, If = 5 }
+
+/// The shim's own expression beside the reference's (quirk Q28; the reference's planner leaves IsNull, Not and Case unimplemented!(),
+/// sql/planner.rs): Not(b), IsNull(x), IsNotNull(x), Coalesce(a, b), NullIf(a, b) and If(c, t, e) — SQL CASE: a NULL condition takes the
+/// else branch — over operands of any form.  Like PhysicalStringExpr it exists on the device only.
+#[derive(Debug)]
+pub struct PhysicalConditionalExpr { pub op: CondOperator, pub operands: Vec<PhysicalExprRef> }
+impl PhysicalConditionalExpr {
+    pub fn create(op: CondOperator, operands: Vec<PhysicalExprRef>) -> PhysicalExprRef { Arc::new(Self { op, operands }) }
+}
+impl PhysicalExpr for PhysicalConditionalExpr {
+    fn as_any(&self) -> &dyn Any { self }
+    fn evaluate(&self, _input: &RecordBatch) -> Result<ColumnValue> {
+        Err(ErrorCode::NotSupported(format!("{:?} is evaluated on the device only (nqe_expr_evaluate)", self.op)))
+    }
+}
+
 fn zero_node() -> NqeExprNode { NqeExprNode { kind: 0, op: 0, column: 0, dtype: 0, is_null: 0, utf8_length: 0, value: NqeValue { i64_: 0 } } }
 
 /// ColumnExpr → column index: prefer idx, else the FIRST field with that name (column.rs:39-57, quirk Q12)
@@ -464,6 +484,9 @@ fn flatten(e: &PhysicalExprRef, schema: &NaiveSchema, out: &mut Vec<NqeExprNode>
         flatten(&m.expr, schema, out, keep)?; // post-order: the string deepest, the pattern on top
         flatten(&m.pattern, schema, out, keep)?;
         out.push(NqeExprNode { kind: NQE_EXPR_STRING_MATCH, op: m.op as i32, ..zero_node() });
+    } else if let Some(c) = e.as_any().downcast_ref::<PhysicalConditionalExpr>() {
+        for a in c.operands.iter() { flatten(a, schema, out, keep)?; } // post-order, operands left to right: If's condition deepest, its else value on top
+        out.push(NqeExprNode { kind: NQE_EXPR_CONDITIONAL, op: c.op as i32, column: c.operands.len() as i32, ..zero_node() });
     } else {
         return Err(ErrorCode::NotSupported("expression kind has no device implementation (cast)".to_string()));
     }

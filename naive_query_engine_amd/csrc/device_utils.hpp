@@ -20,6 +20,15 @@ __device__ __forceinline__ uint64_t lanemask_lt() {
 }
 __device__ __forceinline__ bool get_bit(const uint8_t *bm, int64_t i) { return (bm[i >> 3] >> (i & 7)) & 1; }
 
+// an operand of a node-at-a-time expression kernel (expr_kernels.hpp: binary_kernel; conditional_kernels.hpp): a column or a literal
+struct Operand {
+    const void *values;   // words or packed bits
+    const uint8_t *valid; // or null
+    uint64_t lit;
+    int32_t is_lit;
+    int32_t lit_null;
+};
+
 __device__ __forceinline__ double u2d(uint64_t w) { return __longlong_as_double((long long)w); }
 __device__ __forceinline__ uint64_t d2u(double d) { return (uint64_t)__double_as_longlong(d); }
 

@@ -142,6 +142,23 @@ Value eval_node(nqe_ctx *ctx, const nqe_table *in, const std::vector<Node> &t, i
         v.col = string_match(ctx, x.op, s.col, pat.lit_str, pat.lit_null);
         return v;
     }
+    if (x.kind == NQE_EXPR_CONDITIONAL) { // quirk Q28 (conditional.hip): operands of any form; IF: left = c, right = t, third = e
+        Value k[3];
+        const int ops[3] = {x.left, x.right, x.third};
+        for (int q = 0; q < 3; ++q) {
+            if (ops[q] < 0) continue;
+            k[q] = eval_node(ctx, in, t, ops[q]);
+            const bool value_operand = x.op >= NQE_COND_COALESCE && !(x.op == NQE_COND_IF && q == 0);
+            if (value_operand && k[q].is_lit && k[q].dtype == NQE_UTF8) { // a Utf8 value: a column, as the string nodes expand it
+                k[q].col = utf8_literal_column(ctx, k[q].lit_str, k[q].lit_null, in->rows);
+                k[q].is_lit = false;
+            }
+        }
+        auto arg = [](const Value &o) { return o.is_lit ? CondArg{nullptr, o.lit, o.lit_null} : CondArg{&o.col, 0, false}; };
+        if (x.op == NQE_COND_IF) v.col = conditional(ctx, x.op, x.out_dtype, arg(k[1]), arg(k[2]), arg(k[0]), in->rows);
+        else v.col = conditional(ctx, x.op, k[0].dtype, arg(k[0]), x.right >= 0 ? arg(k[1]) : CondArg{}, CondArg{}, in->rows);
+        return v;
+    }
     Value l = eval_node(ctx, in, t, x.left);
     Value r = eval_node(ctx, in, t, x.right);
     const int64_t n = in->rows;

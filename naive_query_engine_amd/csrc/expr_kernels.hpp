@@ -8,14 +8,7 @@
 namespace nqe {
 namespace {
 
-// ------------------------------------------------------------------ kernels
-struct Operand {
-    const void *values;   // words or packed bits
-    const uint8_t *valid; // or null
-    uint64_t lit;
-    int32_t is_lit;
-    int32_t lit_null;
-};
+// ------------------------------------------------------------------ kernels (their operands: device_utils.hpp, Operand)
 
 // out = a op b, 64 consecutive rows per wave so that ballots form the packed result words.
 // bool_out: result is Boolean (compare / and / or) → packed into out_bits.

@@ -38,7 +38,8 @@ struct Node {
     uint64_t lit = 0;
     std::string lit_str;       // Utf8 literal
     int left = -1, right = -1; // children (indices into the node vector); a UNARY node's operand is `left`
-    int third = -1;            // a STRING_ARGS node's last argument (SUBSTR's len, REPLACE's to): left = s, right = the first argument
+    int third = -1;            // a STRING_ARGS node's last argument (SUBSTR's len, REPLACE's to): left = s, right = the first argument;
+                               // a CONDITIONAL node: left = the first operand (NOT's b, IS_NULL's x, a, IF's c), right = b or t, third = IF's e
     int out_dtype = NQE_NULLTYPE;
 };
 
@@ -46,7 +47,10 @@ bool is_compare(int op) { return op >= NQE_OP_EQ && op <= NQE_OP_GT_EQ; }
 bool is_logic(int op) { return op == NQE_OP_AND || op == NQE_OP_OR; }
 bool is_arith(int op) { return op >= NQE_OP_PLUS && op <= NQE_OP_MODULOS; }
 bool is_string_node(int kind) { return kind == NQE_EXPR_STRING || kind == NQE_EXPR_STRING_ARGS || kind == NQE_EXPR_STRING_MATCH; } // Q25, Q26 and Q27: evaluated node at a time
-bool is_op_node(int kind) { return kind == NQE_EXPR_BINARY || kind == NQE_EXPR_UNARY || is_string_node(kind); } // a node with operands: a step of a program
+bool is_node_at_a_time(int kind) { return is_string_node(kind) || kind == NQE_EXPR_CONDITIONAL; } // Q25-Q27, and Q28's conditional node: no step of the stack machine
+bool is_op_node(int kind) { return kind == NQE_EXPR_BINARY || kind == NQE_EXPR_UNARY || is_node_at_a_time(kind); } // a node with operands: a step of a program
+// the values a CONDITIONAL node's function pops (quirk Q28); 0: `op` is outside nqe_cond_operator
+int cond_arity(int op) { return op < NQE_COND_NOT || op > NQE_COND_IF ? 0 : op <= NQE_COND_IS_NOT_NULL ? 1 : op == NQE_COND_IF ? 3 : 2; }
 
 // ------------------------------------------------------------------ fused whole-tree evaluation: the stack machine's program
 // One instruction per BINARY or UNARY node (post-order), whose operands are a literal, a column word (slot k of the program's distinct
@@ -212,6 +216,27 @@ std::vector<Node> parse(const ExprView &in, const nqe_expr_node *nodes, int n, i
             if (pat.kind != NQE_EXPR_LITERAL || pat.dtype != NQE_UTF8) fail(NQE_ERR_NOT_SUPPORTED, "a string match takes a Utf8 literal for the pattern");
             if (pat.lit_str.size() > size_t(NQE_MAX_MATCH_PATTERN)) fail(NQE_ERR_NOT_SUPPORTED, "a pattern of more than NQE_MAX_MATCH_PATTERN bytes");
             x.out_dtype = x.op == NQE_MATCH_STRPOS ? NQE_INT64 : NQE_BOOLEAN;
+        } else if (nd.kind == NQE_EXPR_CONDITIONAL) { // quirk Q28: not / is_null / is_not_null / coalesce / nullif / if (conditional.hip)
+            if (nd.column < 1 || nd.column > 3) fail(NQE_ERR_INVALID_ARGUMENT, "a conditional node pops one to three values (its `column` field)");
+            x.op = nd.op;
+            const int pops = cond_arity(x.op);
+            if (pops == 0) fail(NQE_ERR_INVALID_ARGUMENT, "unknown conditional operator");
+            if (nd.column != pops) fail(NQE_ERR_INVALID_ARGUMENT, "a conditional node whose `column` field is not its function's arity");
+            if (st.size() < size_t(pops)) fail(NQE_ERR_INVALID_ARGUMENT, "malformed expression");
+            if (pops == 3) { x.third = st.back(); st.pop_back(); }
+            if (pops >= 2) { x.right = st.back(); st.pop_back(); }
+            x.left = st.back(); st.pop_back();
+            for (int a : {x.left, x.right, x.third})
+                if (a >= 0 && t[size_t(a)].out_dtype == NQE_NULLTYPE) fail(NQE_ERR_NOT_SUPPORTED, "Null-typed arrays are not supported on the device path");
+            const int first = t[size_t(x.left)].out_dtype;
+            if ((x.op == NQE_COND_NOT || x.op == NQE_COND_IF) && first != NQE_BOOLEAN)
+                fail(NQE_ERR_INTERVAL, "Cannot evaluate Not / If with a non-Boolean condition");
+            if (pops >= 2) {
+                const int adt = t[size_t(pops == 3 ? x.right : x.left)].out_dtype, bdt = t[size_t(pops == 3 ? x.third : x.right)].out_dtype;
+                if (adt != bdt) fail(NQE_ERR_INTERVAL, "Cannot evaluate conditional expression with types " + std::to_string(adt) + " and " + std::to_string(bdt));
+                x.out_dtype = adt;
+            } else
+                x.out_dtype = NQE_BOOLEAN;
         } else {
             fail(NQE_ERR_INVALID_ARGUMENT, "unknown expression node kind");
         }
@@ -276,7 +301,7 @@ bool match_simple(const std::vector<Node> &t, int i, SimpleExpr *s) {
         for (int k = 0; k < SIMPLE_MAX_OPS; ++k) s->aux[k].pow2_shift = s->aux[k].more = -1;
         return true; // a bare column of any type (Utf8 included) passes through
     }
-    if (x.kind != NQE_EXPR_BINARY || is_logic(x.op)) return false; // (a UNARY, STRING or STRING_MATCH step anywhere below ends the chain here too)
+    if (x.kind != NQE_EXPR_BINARY || is_logic(x.op)) return false; // (a UNARY, STRING, STRING_MATCH or CONDITIONAL step anywhere below ends the chain here too)
     const Node &l = t[size_t(x.left)], &r = t[size_t(x.right)];
     bool lit_left;
     int sub;
@@ -311,7 +336,7 @@ bool build_program(const ExprView &in, const std::vector<Node> &t, int root, ExP
         st.pop_back();
         const Node &x = t[size_t(i)];
         if (!is_op_node(x.kind)) continue;
-        if (is_string_node(x.kind)) return false; // the machine works on 8-byte words: a tree with a string step anywhere goes node at a time
+        if (is_node_at_a_time(x.kind)) return false; // the machine works on 8-byte words and has no select: a tree that holds a string or conditional node goes node at a time
         if (done) { order.push_back(i); continue; }
         st.push_back({i, true});
         if (x.kind == NQE_EXPR_BINARY) st.push_back({x.right, false});
@@ -490,7 +515,7 @@ bool match_conj(const ExprView &in, const nqe_expr_node *nodes, int n, ConjPred 
     // first node of the subtree that ends at node i
     int start[MAXN], stack[MAXN], sp = 0;
     for (int i = 0; i < n; ++i) {
-        if (nodes[i].kind == NQE_EXPR_UNARY || is_string_node(nodes[i].kind)) return false; // (a test is `col [arith lit] cmp lit`: no one-operand step; such trees go through expr_tree_kernel, or node at a time)
+        if (nodes[i].kind == NQE_EXPR_UNARY || is_node_at_a_time(nodes[i].kind)) return false; // (a test is `col [arith lit] cmp lit`: no one-operand step; such trees go through expr_tree_kernel, or node at a time)
         if (nodes[i].kind == NQE_EXPR_BINARY) {
             if (sp < 2) return false;
             sp -= 2;

@@ -349,6 +349,20 @@ DevColumn string_replace(nqe_ctx *ctx, const DevColumn &src, const std::string &
 // string_match.hip: an NQE_EXPR_STRING_MATCH node (quirk Q27) over the Utf8 column `src`: `op` is a nqe_match_operator, the pattern a Utf8
 // literal the parser has checked; Boolean, or Int64 for STRPOS, with src's validity (all NULL under a NULL pattern)
 DevColumn string_match(nqe_ctx *ctx, int op, const DevColumn &src, const std::string &pattern, bool pattern_null);
+// (string_args.hip) `lens` (n + 1 counts in out->values) become the offsets and the data buffer is allocated — after the 64-bit total has been
+// read back and found to fit (more than 2^31-1 bytes: NQE_ERR_ARROW, nothing allocated).  Returns the total; 0: nothing to copy, and
+// `out` holds n empty rows (utf8_empty_rows: offsets of zeros, no bytes, nothing launched).
+uint32_t utf8_size_output(nqe_ctx *ctx, const BufRef &total64, int64_t n, DevColumn *out);
+void utf8_empty_rows(nqe_ctx *ctx, int64_t n, DevColumn *out);
+// conditional.hip: an NQE_EXPR_CONDITIONAL node (quirk Q28).  An operand is a column or, when `col` is null, a literal; Utf8 operands of
+// COALESCE, NULLIF and IF are columns (the caller expands literals).  `a` is the one operand of NOT / IS_NULL / IS_NOT_NULL; a and b are
+// COALESCE's and NULLIF's; IF takes the condition `c` and t = a, e = b.  `dtype` is the value operands' (the parser has checked them).
+struct CondArg {
+    const DevColumn *col = nullptr;
+    uint64_t lit = 0;
+    bool lit_null = false;
+};
+DevColumn conditional(nqe_ctx *ctx, int op, int dtype, const CondArg &a, const CondArg &b, const CondArg &c, int64_t n);
 // general tree `nodes` over the rows of `km`, compacted in the same pass; false = does not fit the stack machine
 bool evaluate_expr_compacted(nqe_ctx *ctx, const nqe_table *in, const nqe_expr_node *nodes, int n, const KeepMask &km, DevColumn *result);
 // the whole projection list behind a selection in ONE run-time specialised kernel (expr_jit.hpp); false when the list does not fit it

@@ -34,8 +34,10 @@ void result_validity(nqe_ctx *ctx, const DevColumn &src, const DevColumn *a1, co
 // a NULL literal argument: every row NULL and empty
 DevColumn all_null(nqe_ctx *ctx, int64_t n) { return utf8_literal_column(ctx, std::string(), true, n); }
 
+} // namespace
+
 // every result row is empty: offsets of zeros, no bytes, nothing launched
-void empty_rows(nqe_ctx *ctx, int64_t n, DevColumn *out) {
+void utf8_empty_rows(nqe_ctx *ctx, int64_t n, DevColumn *out) {
     out->values = dev_alloc_zero(ctx, size_t(n + 1) * 4 + 8);
     out->data = dev_alloc(ctx, 8);
     out->data_length = 0;
@@ -43,11 +45,11 @@ void empty_rows(nqe_ctx *ctx, int64_t n, DevColumn *out) {
 
 // `lens` (n + 1 counts in out->values) become the offsets and the data buffer is allocated — after the 64-bit total has been read back and
 // found to fit.  Returns the total; 0: nothing to copy.
-uint32_t size_output(nqe_ctx *ctx, const BufRef &total64, int64_t n, DevColumn *out) {
+uint32_t utf8_size_output(nqe_ctx *ctx, const BufRef &total64, int64_t n, DevColumn *out) {
     const unsigned long long total = read_scalar(ctx, (const unsigned long long *)total64->ptr);
     if (total > strargs::MAX_TOTAL) fail(NQE_ERR_ARROW, "offset overflow: the result holds " + std::to_string(total) + " bytes, int32 offsets address 2^31-1");
     if (total == 0) {
-        empty_rows(ctx, n, out);
+        utf8_empty_rows(ctx, n, out);
         return 0;
     }
     exclusive_scan_u32_inplace(ctx, (uint32_t *)out->values->ptr, n + 1);
@@ -55,8 +57,6 @@ uint32_t size_output(nqe_ctx *ctx, const BufRef &total64, int64_t n, DevColumn *
     out->data = dev_alloc(ctx, size_t(total) + 8);
     return uint32_t(total);
 }
-
-} // namespace
 
 DevColumn string_substr(nqe_ctx *ctx, const DevColumn &src, const StrIntArg &start, const StrIntArg &len) {
     const int64_t n = src.length, bytes = src.data_length;
@@ -73,7 +73,7 @@ DevColumn string_substr(nqe_ctx *ctx, const DevColumn &src, const StrIntArg &sta
     uint64_t lo, hi;
     const bool empty_window = !start.col && !len.col && !strargs::substr_window(start.lit, len.lit, &lo, &hi);
     if (bytes == 0 || !src.data || empty_window) { // every string is empty already, or the literal window holds no character
-        empty_rows(ctx, n, &out);
+        utf8_empty_rows(ctx, n, &out);
         return out;
     }
     const int32_t *off = (const int32_t *)src.values->ptr;
@@ -108,7 +108,7 @@ DevColumn string_repeat(nqe_ctx *ctx, const DevColumn &src, const StrIntArg &tim
     out.length = n;
     result_validity(ctx, src, times.col, nullptr, &out);
     if (bytes == 0 || !src.data || (!times.col && times.lit <= 0)) {
-        empty_rows(ctx, n, &out);
+        utf8_empty_rows(ctx, n, &out);
         return out;
     }
     const int32_t *off = (const int32_t *)src.values->ptr;
@@ -116,7 +116,7 @@ DevColumn string_repeat(nqe_ctx *ctx, const DevColumn &src, const StrIntArg &tim
     BufRef total64 = dev_alloc_zero(ctx, 8);
     launch(ctx, "str_repeat_lengths", str_repeat_lengths_kernel, dim3(stream_grid(ctx, n, 256)), dim3(256), 0, off, src.valid(), view_of(times), n, (uint32_t *)out.values->ptr,
            (unsigned long long *)total64->ptr);
-    const uint32_t total = size_output(ctx, total64, n, &out);
+    const uint32_t total = utf8_size_output(ctx, total64, n, &out);
     if (total) {
         const int lg = lanes_log2(total, n); // from the OUTPUT's mean: one short string repeated a million times is a whole group's work
         launch(ctx, "str_repeat_copy", NQE_STR_PICK(str_repeat_copy_kernel, lg), dim3(group_grid(ctx, n, lg)), dim3(256), 0, off, (const uint8_t *)src.data->ptr,
@@ -163,7 +163,7 @@ DevColumn string_replace(nqe_ctx *ctx, const DevColumn &src, const std::string &
     BufRef total64 = dev_alloc_zero(ctx, 8);
     launch(ctx, "str_replace_count", NQE_STR_PICK(str_replace_count_kernel, lg), dim3(group_grid(ctx, n, lg)), dim3(256), 0, off, data, src.valid(), d_from, m, t, bordered, n,
            (uint32_t *)out.values->ptr, (unsigned long long *)total64->ptr);
-    const uint32_t total = size_output(ctx, total64, n, &out);
+    const uint32_t total = utf8_size_output(ctx, total64, n, &out);
     if (total)
         launch(ctx, "str_replace_emit", NQE_STR_PICK(str_replace_emit_kernel, lg), dim3(group_grid(ctx, n, lg)), dim3(256), 0, off, data, src.valid(), d_from, d_to, m, t, bordered,
                (const uint32_t *)out.values->ptr, (uint8_t *)out.data->ptr, n);

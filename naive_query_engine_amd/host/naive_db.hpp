@@ -368,6 +368,30 @@ struct PhysicalStringMatchExpr : PhysicalExpr {
     }
 };
 
+// This mirror's own node beside the reference's (quirk Q28: the reference's planner leaves IsNull, Not and Case unimplemented!(),
+// sql/planner.rs): Not(b), IsNull(x), IsNotNull(x), Coalesce(a, b), NullIf(a, b) and If(c, t, e) — SQL CASE: a NULL condition takes the else
+// branch — over operands of any form.  Flattened post-order, operands left to right; the node's `column` carries their number.
+constexpr int32_t EXPR_CONDITIONAL = NQE_EXPR_CONDITIONAL; // 7: a #define beside nqe_expr_kind, whose enumerator list is frozen
+static_assert(EXPR_CONDITIONAL == 7, "the conditional node's kind");
+enum class CondOperator : int32_t { Not = 0, IsNull = 1, IsNotNull = 2, Coalesce = 3, NullIf = 4, If = 5 }; // nqe_cond_operator's order
+struct PhysicalConditionalExpr : PhysicalExpr {
+    CondOperator op;
+    std::vector<PhysicalExprRef> operands;
+    static PhysicalExprRef create(CondOperator op, std::vector<PhysicalExprRef> operands) {
+        auto s = std::make_shared<PhysicalConditionalExpr>();
+        s->op = op; s->operands = std::move(operands);
+        return s;
+    }
+    void flatten(const NaiveSchema &schema, std::vector<nqe_expr_node> &out) const override {
+        for (const PhysicalExprRef &a : operands) a->flatten(schema, out);
+        nqe_expr_node n{};
+        n.kind = NQE_EXPR_CONDITIONAL;
+        n.op = int32_t(op);
+        n.column = int32_t(operands.size());
+        out.push_back(n);
+    }
+};
+
 // ---------------------------------------------------------------- datasource/memory.rs
 struct TableSource {
     virtual ~TableSource() = default;
@@ -1303,6 +1327,13 @@ struct WindowFunctionEx {
                 if (st.size() >= 2) {
                     st.pop_back();
                     st.back() = n.op == NQE_MATCH_STRPOS ? DataType::Int64 : DataType::Boolean;
+                }
+            } else if (n.kind == NQE_EXPR_CONDITIONAL) { // quirk Q28: pops `column` values; the value operands' type (If's else is on top), Boolean for the one-operand forms
+                const size_t pops = size_t(n.column);
+                if (pops >= 1 && st.size() >= pops) {
+                    const DataType top = st.back();
+                    st.resize(st.size() - pops + 1);
+                    st.back() = n.op <= NQE_COND_IS_NOT_NULL ? DataType::Boolean : top;
                 }
             } else if (n.kind == NQE_EXPR_BINARY && st.size() >= 2) {
                 st.pop_back();

@@ -22,7 +22,7 @@ from typing import List, Optional, Sequence, Tuple
 
 from . import capi
 from .arrow_host import AggregateFunc, Column, DType, ErrorCode, Field, Operator, RecordBatch, ScalarValue, SetOp, Status, UnaryOperator, WindowFrame, WindowFrameEx, WindowFunc, WindowFuncEx
-from .expression import ColumnExpr, MatchOperator, PhysicalBinaryExpr, PhysicalExpr, PhysicalLiteralExpr, PhysicalStringArgsExpr, PhysicalStringExpr, PhysicalStringMatchExpr
+from .expression import ColumnExpr, CondOperator, MatchOperator, PhysicalBinaryExpr, PhysicalConditionalExpr, PhysicalExpr, PhysicalLiteralExpr, PhysicalStringArgsExpr, PhysicalStringExpr, PhysicalStringMatchExpr
 
 NaiveSchema = List[Field]  # src/logical_plan/schema.rs (qualifiers are ignored at physical planning, Q12)
 
@@ -904,7 +904,10 @@ _COMPARISONS = (Operator.Eq, Operator.NotEq, Operator.Lt, Operator.LtEq, Operato
 
 def _static_dtype(expr: PhysicalExpr, schema: NaiveSchema) -> DType:
     """the dtype an expression evaluates to (Q6: no coercion, so an arithmetic node has its left operand's; a unary function Float64; a string
-    function Utf8, CharacterLength Int64; substr / repeat / replace Utf8; a string match Boolean, strpos Int64)"""
+    function Utf8, CharacterLength Int64; substr / repeat / replace Utf8; a string match Boolean, strpos Int64;
+    Not / IsNull / IsNotNull Boolean, Coalesce / NullIf their first operand's, If its `then` operand's)"""
+    if isinstance(expr, PhysicalConditionalExpr):
+        return DType.BOOLEAN if expr.op in (CondOperator.Not, CondOperator.IsNull, CondOperator.IsNotNull) else _static_dtype(expr.operands[1 if expr.op == CondOperator.If else 0], schema)
     if isinstance(expr, PhysicalStringMatchExpr):
         return DType.INT64 if expr.op == MatchOperator.StrPos else DType.BOOLEAN
     if isinstance(expr, PhysicalStringArgsExpr):
