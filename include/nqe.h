@@ -146,11 +146,17 @@ typedef struct nqe_column {
  * the else value on top). In postfix: `b NOT`, `x IS_NULL`, `a b COALESCE`, `a b NULLIF`,
  * `c t e IF`; coalesce(a, b, c) is `a b c COALESCE COALESCE`, CASE WHEN c1 THEN x WHEN c2 THEN y
  * ELSE z END is `c1 x c2 y z IF IF`, and a CASE without ELSE takes a NULL literal as `e`. A
- * reader of the flat encoding can walk the stack by `column` alone. */
+ * reader of the flat encoding can walk the stack by `column` alone.
+ * A CAST node (quirk Q29: PhysicalCastExpr, whose body the reference leaves todo!(),
+ * physical_plan/expression/cast.rs) is NQE_EXPR_CAST = 8, a #define beside the enum for the same
+ * reason. It pops ONE value and pushes one; its `dtype` field carries the target nqe_dtype; `op`,
+ * `column` and the literal fields are not read. In postfix: `x CAST`. */
 typedef enum nqe_expr_kind { NQE_EXPR_COLUMN = 0, NQE_EXPR_LITERAL = 1, NQE_EXPR_BINARY = 2, NQE_EXPR_UNARY = 3, NQE_EXPR_STRING = 4, NQE_EXPR_STRING_ARGS = 5, NQE_EXPR_STRING_MATCH } nqe_expr_kind;
 typedef char nqe_expr_string_match_is_6[(NQE_EXPR_STRING_MATCH == 6) ? 1 : -1];
 #define NQE_EXPR_CONDITIONAL 7
 typedef char nqe_expr_conditional_is_7[(NQE_EXPR_CONDITIONAL == NQE_EXPR_STRING_MATCH + 1) ? 1 : -1];
+#define NQE_EXPR_CAST 8
+typedef char nqe_expr_cast_is_8[(NQE_EXPR_CAST == NQE_EXPR_CONDITIONAL + 1) ? 1 : -1];
 
 /* the `op` of a CONDITIONAL node (quirk Q28; see nqe_expr_evaluate) */
 typedef enum nqe_cond_operator {
@@ -207,7 +213,7 @@ typedef struct nqe_expr_node {
     int32_t kind;    /* nqe_expr_kind */
     int32_t op;      /* BINARY: nqe_operator; UNARY, STRING and STRING_ARGS: nqe_unary_operator; STRING_MATCH: nqe_match_operator; CONDITIONAL: nqe_cond_operator */
     int32_t column;  /* COLUMN: index into the input batch; CONDITIONAL: the number of values the node pops (its arity) */
-    int32_t dtype;   /* LITERAL: nqe_dtype of the ScalarValue */
+    int32_t dtype;   /* LITERAL: nqe_dtype of the ScalarValue; CAST: the target nqe_dtype */
     int32_t is_null; /* LITERAL: 1 = ScalarValue::X(None) */
     int32_t utf8_length; /* LITERAL of dtype NQE_UTF8: byte length of value.utf8 (the field was `reserved` before Utf8
                             literals existed; the struct layout is unchanged) */
@@ -601,7 +607,46 @@ nqe_status nqe_sharded_selection_projection_execute(nqe_comm *comm, const nqe_ta
  * NQE_ERR_INVALID_ARGUMENT; fewer values than the node pops → NQE_ERR_INVALID_ARGUMENT; an
  * operand of dtype NQE_NULLTYPE → NQE_ERR_NOT_SUPPORTED; NOT's operand or IF's `c` not Boolean →
  * NQE_ERR_INTERVAL; the two value operands of COALESCE, NULLIF or IF of different dtypes →
- * NQE_ERR_INTERVAL. */
+ * NQE_ERR_INTERVAL.
+ * Casts (NQE_EXPR_CAST, quirk Q29): `x CAST` converts x, of any form, to the nqe_dtype in the
+ * node's `dtype` field. There is no implicit coercion (a dtype mismatch stays NQE_ERR_INTERVAL):
+ * the cast is how `id * 1.5`, `v > 0` or `coalesce(v, 0)` cross dtypes. The rules are arrow's
+ * cast with safe = true, restated: a conversion that cannot represent the value gives NULL; it
+ * is never an error and never wraps. A NULL operand row is a NULL result row; under a NULL
+ * result row the word is 0, the Boolean bit is 0 and a Utf8 row is empty; the bits of the last
+ * value or validity word beyond the row count are 0.
+ *   same dtype                       the operand itself, as a bare column evaluates (a literal is
+ *                                    expanded to in.num_rows rows)
+ *   Int64 -> UInt64                  NULL iff v < 0
+ *   UInt64 -> Int64                  NULL iff v >= 2^63
+ *   Int64 / UInt64 -> Float64        the nearest binary64, ties to even; always valid
+ *   Float64 -> Int64                 NULL iff NaN, x < -2^63 or x >= 2^63; else truncation toward zero
+ *   Float64 -> UInt64                NULL iff NaN, x <= -1.0 or x >= 2^64; else truncation toward
+ *                                    zero, so -0.5 and -0.0 give 0
+ *   Boolean -> Int64/UInt64/Float64  0 / 1, or 0.0 / 1.0
+ *   Boolean -> Utf8                  `true` / `false`
+ *   Int64/UInt64/Float64 -> Boolean  v != 0, so NaN is true and -0.0 is false
+ *   Int64 / UInt64 -> Utf8           the shortest decimal, a leading `-` for negatives, no `+`
+ *                                    (INT64_MIN is 20 bytes)
+ *   Utf8 -> Int64                    [+-]digits+ over the slot's bytes; anything else is NULL: the
+ *                                    empty string, blanks, overflow, `1e3`, `1.0`
+ *   Utf8 -> UInt64                   [+]digits+; above 2^64-1 is NULL; any `-` is NULL, `-0` included
+ *   Utf8 -> Float64                  the CSV reader's grammar ([+-] (digits [. digits*] | . digits+)
+ *                                    [(e|E) [+-] digits+] | [+-] (nan | inf | infinity), ASCII
+ *                                    case-insensitive), correctly rounded; anything else is NULL
+ *   Utf8 -> Boolean                  `true` / `false`, ASCII case-insensitive; anything else is NULL
+ * Nothing trims the input: cast(trim(s) as bigint) composes. A result carries a validity buffer
+ * only where the static form can be NULL. The infallible casts (same dtype, Int64 / UInt64 ->
+ * Float64, Boolean -> anything, numeric -> Boolean, Int64 / UInt64 -> Utf8) carry one iff the
+ * operand does: the operand's buffer, shared where an output may alias it, else copied, with the
+ * operand's null_count. The fallible casts (Int64 <-> UInt64, Float64 -> Int64 / UInt64, Utf8 ->
+ * anything) always carry one, with null_count -1. Zero rows give a well-formed column. A Utf8
+ * result of more than 2^31-1 bytes fails with NQE_ERR_ARROW before the data buffer is allocated.
+ * A tree that holds the node is evaluated node at a time. Errors, in this order, before anything
+ * is allocated or launched: `dtype` outside NQE_BOOLEAN..NQE_UTF8 → NQE_ERR_INVALID_ARGUMENT; no
+ * operand on the stack → NQE_ERR_INVALID_ARGUMENT; an operand of dtype NQE_NULLTYPE →
+ * NQE_ERR_NOT_SUPPORTED; Float64 -> Utf8 → NQE_ERR_NOT_SUPPORTED (shortest-round-trip digit
+ * generation is not part of this library yet). */
 nqe_status nqe_expr_evaluate(nqe_ctx *ctx, const nqe_table *in, const nqe_expr_node *nodes,
                              int32_t num_nodes, nqe_table **out);
 

@@ -23,8 +23,8 @@
 //!   4. `pub(crate)` on the fields of `ScanPlan` (scan.rs:19-22), `SelectionPlan` (selection.rs:23-27), `ProjectionPlan`
 //!      (projection.rs:18-23), `HashJoin::{left,right,on,schema}` (hash_join.rs:44-56), `CrossJoin::{left,right,schema}` (cross_join.rs:26-32),
 //!      `NestedLoopJoin::{left,right,on,schema}` (nested_loop_join.rs:31-38), `PhysicalLimitPlan` (limit.rs:15-19),
-//!      `PhysicalOffsetPlan` (offset.rs:15-19), `PhysicalBinaryExpr` (expression/binary.rs:91-96) and `PhysicalUnaryExpr::{expr,func}`
-//!      (expression/unary.rs:46-51).
+//!      `PhysicalOffsetPlan` (offset.rs:15-19), `PhysicalBinaryExpr` (expression/binary.rs:91-96), `PhysicalUnaryExpr::{expr,func}`
+//!      (expression/unary.rs:46-51) and `PhysicalCastExpr::{expr,data_type}` (expression/cast.rs:16-20).
 //!   5. `src/physical_plan/aggregate/mod.rs:225`: one more method on `trait AggregateOperator`, one line in each of
 //!      sum.rs / avg.rs / count.rs / max.rs / min.rs:
 //!          `fn describe(&self) -> (AggregateFunc, ColumnExpr);`             (e.g. `(AggregateFunc::Sum, self.col_expr.clone())`)
@@ -54,7 +54,7 @@ use crate::logical_plan::expression::{AggregateFunc, Column, ScalarValue, UnaryO
 use crate::logical_plan::plan::JoinType;
 use crate::logical_plan::schema::{NaiveField, NaiveSchema};
 use crate::physical_plan::{
-    ColumnExpr, CrossJoin, HashJoin, NestedLoopJoin, PhysicalAggregatePlan, PhysicalBinaryExpr, PhysicalExpr, PhysicalExprRef, PhysicalLimitPlan, PhysicalLiteralExpr, PhysicalOffsetPlan,
+    ColumnExpr, CrossJoin, HashJoin, NestedLoopJoin, PhysicalAggregatePlan, PhysicalBinaryExpr, PhysicalCastExpr, PhysicalExpr, PhysicalExprRef, PhysicalLimitPlan, PhysicalLiteralExpr, PhysicalOffsetPlan,
     PhysicalPlan, PhysicalPlanRef, PhysicalUnaryExpr, ProjectionPlan, ScanPlan, SelectionPlan,
 };
 
@@ -106,6 +106,7 @@ const NQE_EXPR_STRING: i32 = 4; // quirk Q25: the shim's own PhysicalStringExpr 
 const NQE_EXPR_STRING_ARGS: i32 = 5; // quirk Q26: the shim's own PhysicalStringArgsExpr below
 const NQE_EXPR_STRING_MATCH: i32 = 6; // quirk Q27: the shim's own PhysicalStringMatchExpr below
 const NQE_EXPR_CONDITIONAL: i32 = 7; // quirk Q28: the shim's own PhysicalConditionalExpr below; the node's `column` carries the number of values it pops
+const NQE_EXPR_CAST: i32 = 8; // quirk Q29: the reference's own PhysicalCastExpr (its evaluate is todo!(), cast.rs:45-87); the node's `dtype` carries the target
 const NQE_BOOLEAN: i32 = 1; const NQE_INT64: i32 = 2; const NQE_UINT64: i32 = 3; const NQE_FLOAT64: i32 = 4; const NQE_UTF8: i32 = 5;
 
 extern "C" {
@@ -487,8 +488,17 @@ fn flatten(e: &PhysicalExprRef, schema: &NaiveSchema, out: &mut Vec<NqeExprNode>
     } else if let Some(c) = e.as_any().downcast_ref::<PhysicalConditionalExpr>() {
         for a in c.operands.iter() { flatten(a, schema, out, keep)?; } // post-order, operands left to right: If's condition deepest, its else value on top
         out.push(NqeExprNode { kind: NQE_EXPR_CONDITIONAL, op: c.op as i32, column: c.operands.len() as i32, ..zero_node() });
+    } else if let Some(c) = e.as_any().downcast_ref::<PhysicalCastExpr>() {
+        // post-order: `x CAST`, the target type in the node's `dtype`.  A type nqe_dtype has no name for goes as 0, which the library
+        // refuses first (InvalidArgument); Float64 -> Utf8 comes back NotSupported.  The rules: include/nqe.h (arrow's safe cast, restated)
+        flatten(&c.expr, schema, out, keep)?;
+        let dtype = match c.data_type {
+            DataType::Boolean => NQE_BOOLEAN, DataType::Int64 => NQE_INT64, DataType::UInt64 => NQE_UINT64,
+            DataType::Float64 => NQE_FLOAT64, DataType::Utf8 => NQE_UTF8, _ => 0, // → NQE_ERR_INVALID_ARGUMENT
+        };
+        out.push(NqeExprNode { kind: NQE_EXPR_CAST, dtype, ..zero_node() });
     } else {
-        return Err(ErrorCode::NotSupported("expression kind has no device implementation (cast)".to_string()));
+        return Err(ErrorCode::NotSupported("expression kind has no device implementation".to_string()));
     }
     Ok(())
 }

@@ -9,20 +9,20 @@ Layout:
   arrow_host.py    numpy-backed Arrow-layout host containers (plumbing)
   expression.py    host mirror of ColumnExpr / PhysicalLiteralExpr / PhysicalBinaryExpr / PhysicalUnaryExpr / PhysicalStringExpr /
                    PhysicalStringArgsExpr (substr, repeat, replace) / PhysicalStringMatchExpr (like, ilike, starts_with, ends_with, contains, strpos) /
-                   PhysicalConditionalExpr (not_, is_null, is_not_null, coalesce, nullif, if_else, case_when)
+                   PhysicalConditionalExpr (not_, is_null, is_not_null, coalesce, nullif, if_else, case_when) / PhysicalCastExpr (cast)
   physical_plan.py host mirror of the PhysicalPlan operators (ScanPlan, SelectionPlan, ...)
   rewrite.py       plan rewrite pass (unfused reference-shaped tree → fused device operators), Catalog / NaiveDB surface
   parallel.py      row-range sharding across GPUs: thin caller of the C ABI's sharded entry points (RCCL)
 """
 from .arrow_host import (AggregateFunc, Column, DType, ErrorCode, Field, Operator, RecordBatch, ScalarValue, SetOp, Status,
                          UnaryOperator, WindowFrame, WindowFrameEx, WindowFunc, WindowFuncEx, read_csv)
-from .expression import (ColumnExpr, CondOperator, MatchOperator, PhysicalBinaryExpr, PhysicalConditionalExpr, PhysicalExpr, PhysicalLiteralExpr, PhysicalStringArgsExpr, PhysicalStringExpr,
+from .expression import (ColumnExpr, CondOperator, MatchOperator, PhysicalBinaryExpr, PhysicalCastExpr, PhysicalConditionalExpr, PhysicalExpr, PhysicalLiteralExpr, PhysicalStringArgsExpr, PhysicalStringExpr,
                          PhysicalStringMatchExpr, PhysicalUnaryExpr)
 
 __all__ = [
     "AggregateFunc", "Column", "DType", "ErrorCode", "Field", "Operator", "RecordBatch", "ScalarValue", "Status",
     "read_csv", "ColumnExpr", "PhysicalBinaryExpr", "PhysicalExpr", "PhysicalLiteralExpr", "PhysicalUnaryExpr", "UnaryOperator",
-    "PhysicalStringExpr", "PhysicalStringArgsExpr", "PhysicalStringMatchExpr", "MatchOperator", "PhysicalConditionalExpr", "CondOperator",
+    "PhysicalStringExpr", "PhysicalStringArgsExpr", "PhysicalStringMatchExpr", "MatchOperator", "PhysicalConditionalExpr", "CondOperator", "PhysicalCastExpr",
     "WindowFrame", "WindowFunc", "SetOp", "WindowFrameEx", "WindowFuncEx",
 ]
 

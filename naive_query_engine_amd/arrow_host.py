@@ -211,6 +211,7 @@ EXPR_STRING = 4  # quirk Q25: a string function with a body (NQE_EXPR_STRING); `
 EXPR_STRING_ARGS = 5  # quirk Q26: substr / repeat / replace (NQE_EXPR_STRING_ARGS); pops the string and its two (repeat: one) arguments
 EXPR_STRING_MATCH = 6  # quirk Q27: like / ilike / starts_with / ends_with / contains / strpos (NQE_EXPR_STRING_MATCH); pops the string and the pattern literal
 EXPR_CONDITIONAL = 7  # quirk Q28: not / is_null / is_not_null / coalesce / nullif / if (NQE_EXPR_CONDITIONAL); `column` carries the number of values it pops
+EXPR_CAST = 8  # quirk Q29: PhysicalCastExpr (NQE_EXPR_CAST); pops one value, the node's `dtype` carries the target type
 HOST, DEVICE = 0, 1
 
 _WORD_NP = {DType.INT64: np.int64, DType.UINT64: np.uint64, DType.FLOAT64: np.float64}
@@ -575,6 +576,13 @@ def node_conditional(op: "CondOperator", arity: int) -> NqeExprNode:
     n.kind = EXPR_CONDITIONAL
     n.op = int(op)
     n.column = int(arity)  # the values the node pops: the library checks it against the function's arity
+    return n
+
+
+def node_cast(dtype: "DType") -> NqeExprNode:
+    n = NqeExprNode()
+    n.kind = EXPR_CAST
+    n.dtype = int(dtype)  # the target type: the library refuses what is not Boolean .. Utf8
     return n
 
 

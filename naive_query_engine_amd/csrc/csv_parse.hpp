@@ -18,7 +18,7 @@
 
 #if defined(__HIPCC__)
 #define NQE_HD __host__ __device__ inline
-#define NQE_HD_COLD __host__ __device__ __noinline__ // big-integer paths: kept out of the kernels' hot code
+#define NQE_HD_COLD __host__ __device__ __noinline__ inline // big-integer paths: kept out of the kernels' hot code (`inline` for linkage alone: csv.hip and cast.hip both hold them)
 #else
 #define NQE_HD inline
 #define NQE_HD_COLD inline

@@ -19,6 +19,16 @@ __device__ __forceinline__ uint64_t lanemask_lt() {
     return (1ull << lane_id()) - 1ull;
 }
 __device__ __forceinline__ bool get_bit(const uint8_t *bm, int64_t i) { return (bm[i >> 3] >> (i & 7)) & 1; }
+// small helpers of the string, conditional and cast kernels
+typedef uint64_t __attribute__((aligned(1))) str_u64_unaligned; // unaligned 8-byte access: fine for global memory on gfx9 and later
+// bit j of a validity bitmap that may be absent (null: every row valid)
+__device__ __forceinline__ bool str_bit_at(const uint8_t *v, int64_t j) { return !v || ((v[j >> 3] >> (j & 7)) & 1); } // (bytes: a borrowed bitmap ends at ceil(n / 8))
+// the sum of a 64-bit value over the wave's lanes, added to *total by lane 0
+__device__ __forceinline__ void wave_add_to(unsigned long long v, unsigned long long *total) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
+    if (lane_id() == 0 && v) atomicAdd(total, v);
+}
 
 // an operand of a node-at-a-time expression kernel (expr_kernels.hpp: binary_kernel; conditional_kernels.hpp): a column or a literal
 struct Operand {

@@ -159,6 +159,12 @@ Value eval_node(nqe_ctx *ctx, const nqe_table *in, const std::vector<Node> &t, i
         else v.col = conditional(ctx, x.op, k[0].dtype, arg(k[0]), x.right >= 0 ? arg(k[1]) : CondArg{}, CondArg{}, in->rows);
         return v;
     }
+    if (x.kind == NQE_EXPR_CAST) { // quirk Q29 (cast.hip): a literal is expanded and then cast like a column — there is no folding path
+        Value c = eval_node(ctx, in, t, x.left);
+        if (c.is_lit) c.col = c.dtype == NQE_UTF8 ? utf8_literal_column(ctx, c.lit_str, c.lit_null, in->rows) : materialise_literal(ctx, c.dtype, c.lit, c.lit_null, in->rows);
+        v.col = cast_column(ctx, c.col, x.out_dtype);
+        return v;
+    }
     Value l = eval_node(ctx, in, t, x.left);
     Value r = eval_node(ctx, in, t, x.right);
     const int64_t n = in->rows;

@@ -47,7 +47,7 @@ bool is_compare(int op) { return op >= NQE_OP_EQ && op <= NQE_OP_GT_EQ; }
 bool is_logic(int op) { return op == NQE_OP_AND || op == NQE_OP_OR; }
 bool is_arith(int op) { return op >= NQE_OP_PLUS && op <= NQE_OP_MODULOS; }
 bool is_string_node(int kind) { return kind == NQE_EXPR_STRING || kind == NQE_EXPR_STRING_ARGS || kind == NQE_EXPR_STRING_MATCH; } // Q25, Q26 and Q27: evaluated node at a time
-bool is_node_at_a_time(int kind) { return is_string_node(kind) || kind == NQE_EXPR_CONDITIONAL; } // Q25-Q27, and Q28's conditional node: no step of the stack machine
+bool is_node_at_a_time(int kind) { return is_string_node(kind) || kind == NQE_EXPR_CONDITIONAL || kind == NQE_EXPR_CAST; } // Q25-Q27, Q28's conditional node and Q29's cast: no step of the stack machine
 bool is_op_node(int kind) { return kind == NQE_EXPR_BINARY || kind == NQE_EXPR_UNARY || is_node_at_a_time(kind); } // a node with operands: a step of a program
 // the values a CONDITIONAL node's function pops (quirk Q28); 0: `op` is outside nqe_cond_operator
 int cond_arity(int op) { return op < NQE_COND_NOT || op > NQE_COND_IF ? 0 : op <= NQE_COND_IS_NOT_NULL ? 1 : op == NQE_COND_IF ? 3 : 2; }
@@ -237,6 +237,15 @@ std::vector<Node> parse(const ExprView &in, const nqe_expr_node *nodes, int n, i
                 x.out_dtype = adt;
             } else
                 x.out_dtype = NQE_BOOLEAN;
+        } else if (nd.kind == NQE_EXPR_CAST) { // quirk Q29: `x CAST`, the target in `dtype` (cast.hip)
+            if (nd.dtype < NQE_BOOLEAN || nd.dtype > NQE_UTF8) fail(NQE_ERR_INVALID_ARGUMENT, "a cast node whose `dtype` field is not a target type (Boolean .. Utf8)");
+            if (st.empty()) fail(NQE_ERR_INVALID_ARGUMENT, "malformed expression");
+            x.left = st.back(); st.pop_back();
+            x.dtype = nd.dtype;
+            const int from = t[size_t(x.left)].out_dtype;
+            if (from == NQE_NULLTYPE) fail(NQE_ERR_NOT_SUPPORTED, "Null-typed arrays are not supported on the device path");
+            if (from == NQE_FLOAT64 && nd.dtype == NQE_UTF8) fail(NQE_ERR_NOT_SUPPORTED, "a cast of Float64 to Utf8 (shortest-round-trip digits) is not supported");
+            x.out_dtype = nd.dtype;
         } else {
             fail(NQE_ERR_INVALID_ARGUMENT, "unknown expression node kind");
         }

@@ -363,6 +363,9 @@ struct CondArg {
     bool lit_null = false;
 };
 DevColumn conditional(nqe_ctx *ctx, int op, int dtype, const CondArg &a, const CondArg &b, const CondArg &c, int64_t n);
+// cast.hip: an NQE_EXPR_CAST node (quirk Q29) over the column `src` (the caller expands literals) to the nqe_dtype `to`; the parser has
+// refused Float64 -> Utf8.  An infallible cast carries src's validity, a fallible one a buffer of its own (include/nqe.h).
+DevColumn cast_column(nqe_ctx *ctx, const DevColumn &src, int to);
 // general tree `nodes` over the rows of `km`, compacted in the same pass; false = does not fit the stack machine
 bool evaluate_expr_compacted(nqe_ctx *ctx, const nqe_table *in, const nqe_expr_node *nodes, int n, const KeepMask &km, DevColumn *result);
 // the whole projection list behind a selection in ONE run-time specialised kernel (expr_jit.hpp); false when the list does not fit it

@@ -35,19 +35,13 @@ struct StrArgView {
     int64_t lit;
 };
 __device__ __forceinline__ int64_t str_arg_at(const StrArgView &a, int64_t j) { return a.values ? a.values[j] : a.lit; }
-__device__ __forceinline__ bool str_bit_at(const uint8_t *v, int64_t j) { return !v || ((v[j >> 3] >> (j & 7)) & 1); } // (bytes: a borrowed bitmap ends at ceil(n / 8))
+// (str_bit_at, wave_add_to: device_utils.hpp)
 
 // the bits of a wave's ballot that belong to this lane's group of 2^LG lanes, bit b = lane b of the group
 template <int LG> __device__ __forceinline__ uint64_t group_ballot(bool pred, uint32_t grp) {
     const uint64_t b = __ballot(pred);
     if constexpr (LG == 6) return b;
     else return (b >> (grp << LG)) & ((1ull << (1 << LG)) - 1ull);
-}
-// the sum of a 64-bit value over the wave's lanes, added to *total by lane 0
-__device__ __forceinline__ void wave_add_to(unsigned long long v, unsigned long long *total) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
-    if (lane_id() == 0 && v) atomicAdd(total, v);
 }
 
 template <int LG>

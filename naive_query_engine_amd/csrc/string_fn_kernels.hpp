@@ -21,7 +21,7 @@
 namespace nqe {
 namespace {
 
-typedef uint64_t __attribute__((aligned(1))) str_u64_unaligned; // unaligned 8-byte access: fine for global memory on gfx9 and later
+// (str_u64_unaligned: device_utils.hpp)
 
 // `head` bytes precede the first 16-byte boundary of src AND of dst (the host places dst at src's misalignment), head <= nbytes
 template <bool UPPER>

@@ -392,6 +392,28 @@ struct PhysicalConditionalExpr : PhysicalExpr {
     }
 };
 
+// physical_plan/expression/cast.rs:16-88, whose evaluate is thirty-odd todo!()s (quirk Q29).  Here it has a body on the device: arrow's cast with
+// safe = true over Boolean, Int64, UInt64, Float64 and Utf8 — what the target cannot represent is NULL (the rules: include/nqe.h).  Flattened
+// post-order, `x CAST`, the target in the node's `dtype`; the library refuses what is no target type, and Float64 -> Utf8.
+constexpr int32_t EXPR_CAST = NQE_EXPR_CAST; // 8: a #define beside nqe_expr_kind, whose enumerator list is frozen
+static_assert(EXPR_CAST == 8, "the cast node's kind");
+struct PhysicalCastExpr : PhysicalExpr {
+    PhysicalExprRef expr;
+    DataType data_type;
+    static PhysicalExprRef create(PhysicalExprRef expr, const DataType &data_type) {
+        auto s = std::make_shared<PhysicalCastExpr>();
+        s->expr = std::move(expr); s->data_type = data_type;
+        return s;
+    }
+    void flatten(const NaiveSchema &schema, std::vector<nqe_expr_node> &out) const override {
+        expr->flatten(schema, out);
+        nqe_expr_node n{};
+        n.kind = NQE_EXPR_CAST;
+        n.dtype = int32_t(data_type);
+        out.push_back(n);
+    }
+};
+
 // ---------------------------------------------------------------- datasource/memory.rs
 struct TableSource {
     virtual ~TableSource() = default;
@@ -1335,7 +1357,8 @@ struct WindowFunctionEx {
                     st.resize(st.size() - pops + 1);
                     st.back() = n.op <= NQE_COND_IS_NOT_NULL ? DataType::Boolean : top;
                 }
-            } else if (n.kind == NQE_EXPR_BINARY && st.size() >= 2) {
+            } else if (n.kind == NQE_EXPR_CAST && !st.empty()) st.back() = DataType(n.dtype); // quirk Q29: the target type
+            else if (n.kind == NQE_EXPR_BINARY && st.size() >= 2) {
                 st.pop_back();
                 if (n.op <= NQE_OP_GT_EQ || n.op >= NQE_OP_AND) st.back() = DataType::Boolean;
             }

@@ -22,7 +22,7 @@ from typing import List, Optional, Sequence, Tuple
 
 from . import capi
 from .arrow_host import AggregateFunc, Column, DType, ErrorCode, Field, Operator, RecordBatch, ScalarValue, SetOp, Status, UnaryOperator, WindowFrame, WindowFrameEx, WindowFunc, WindowFuncEx
-from .expression import ColumnExpr, CondOperator, MatchOperator, PhysicalBinaryExpr, PhysicalConditionalExpr, PhysicalExpr, PhysicalLiteralExpr, PhysicalStringArgsExpr, PhysicalStringExpr, PhysicalStringMatchExpr
+from .expression import ColumnExpr, CondOperator, MatchOperator, PhysicalBinaryExpr, PhysicalCastExpr, PhysicalConditionalExpr, PhysicalExpr, PhysicalLiteralExpr, PhysicalStringArgsExpr, PhysicalStringExpr, PhysicalStringMatchExpr
 
 NaiveSchema = List[Field]  # src/logical_plan/schema.rs (qualifiers are ignored at physical planning, Q12)
 
@@ -905,7 +905,9 @@ _COMPARISONS = (Operator.Eq, Operator.NotEq, Operator.Lt, Operator.LtEq, Operato
 def _static_dtype(expr: PhysicalExpr, schema: NaiveSchema) -> DType:
     """the dtype an expression evaluates to (Q6: no coercion, so an arithmetic node has its left operand's; a unary function Float64; a string
     function Utf8, CharacterLength Int64; substr / repeat / replace Utf8; a string match Boolean, strpos Int64;
-    Not / IsNull / IsNotNull Boolean, Coalesce / NullIf their first operand's, If its `then` operand's)"""
+    Not / IsNull / IsNotNull Boolean, Coalesce / NullIf their first operand's, If its `then` operand's; a cast its target)"""
+    if isinstance(expr, PhysicalCastExpr):
+        return DType(expr.data_type)
     if isinstance(expr, PhysicalConditionalExpr):
         return DType.BOOLEAN if expr.op in (CondOperator.Not, CondOperator.IsNull, CondOperator.IsNotNull) else _static_dtype(expr.operands[1 if expr.op == CondOperator.If else 0], schema)
     if isinstance(expr, PhysicalStringMatchExpr):

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Reports every kernel of the fast aggregate instantiations and of the string functions (with and without arguments), of string matching and of the conditional functions that spills VGPRs (scratch traffic in a streaming kernel is a 2x cliff)
+# Reports every kernel of the fast aggregate instantiations and of the string functions (with and without arguments), of string matching, of the conditional functions and of the casts that spills VGPRs (scratch traffic in a streaming kernel is a 2x cliff)
 # or uses scratch memory without spilling (a by-value kernel argument indexed at run time lands there: 3.7x slower, found once).
 cd "$(dirname "$0")/../naive_query_engine_amd/csrc"
 for pv in 0:0 0:1 1:0 1:1 2:0 2:1 3:0 3:1 4:0; do p=${pv%:*}; v=${pv#*:}
@@ -18,6 +18,9 @@ done
 # ... and of the conditional functions (conditional.hip: cond_words, cond_bits, cond_str_lengths, cond_str_copy)
 ( /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -munsafe-fp-atomics -fno-gpu-rdc $EXTRA -c conditional.hip -o /dev/null -Rpass-analysis=kernel-resource-usage 2>&1 \
     | grep -E "Function Name|VGPRs:|ScratchSize|VGPRs Spill" | sed 's/.*remark: *//; s/ \[-Rpass.*//' | paste - - - - | awk '$NF != 0 || $(NF-3) != 0' | sed 's/Function Name: _ZN3nqe12_GLOBAL__N_1//' > /tmp/spills_conditional.txt ) &
+# ... and of the casts (cast.hip: cast_fixed, cast_parse, cast_text_lengths, cast_text_write)
+( /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -munsafe-fp-atomics -fno-gpu-rdc $EXTRA -c cast.hip -o /dev/null -Rpass-analysis=kernel-resource-usage 2>&1 \
+    | grep -E "Function Name|VGPRs:|ScratchSize|VGPRs Spill" | sed 's/.*remark: *//; s/ \[-Rpass.*//' | paste - - - - | awk '$NF != 0 || $(NF-3) != 0' | sed 's/Function Name: _ZN3nqe12_GLOBAL__N_1//' > /tmp/spills_cast.txt ) &
 wait
 cat /tmp/spills_*.txt | cut -c1-200
 echo "kernels with VGPR spills or scratch: $(cat /tmp/spills_*.txt | wc -l)"
